@@ -5,8 +5,13 @@ One "step" = one complete ``DiscreteDiffusionSDE.sample()`` call: JannerUNet1d (
 k=5), horizon 32, B=256 trajectories per GPU, 20-step DDIM, x-prediction, fix-mask on the first observation,
 temperature 0.5 -- synthetic random-init weights and synthetic inputs already resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (driver, N > 1)
+
+A plain run sets up, warms up, times exactly K steps and prints the headline; everything else it measures or checks (the
+blocks marked [--full] below) runs only with ``--full``.  ``--dump-outputs DIR`` writes what the last timed step returned
+(``DIR/x.npy``, float32, rank 0); the global RNG is seeded right before the timed loop, so with the same arguments the last
+step's inputs -- its initial draw included -- are the same from run to run and two builds can be compared output for output.
 
 The ONE JSON line (rank 0):
 
@@ -14,15 +19,17 @@ The ONE JSON line (rank 0):
   inside the call).  N > 1: STRONG scaling -- the 256 trajectories are cut into 256 / N per rank through
   ``cleandiffuser_amd.distributed.sharded_sample`` (shard, sample, ONE RCCL all-gather of the result inside the timed region: north
   star "RCCL over xGMI used only to gather sampled trajectories"); ``scaling`` says "strong" (north star: ">= 6x strong scaling").
-* ``replayed_noise`` -- the same call with the recorded ``noise=[z0]`` (rounds 1-2's headline), for comparison.
-* ``weak_scaling`` (N > 1) -- every rank its own 256 trajectories + the all-gather of N x 256;  ``strong_scaling.global_batch_3200``
+  ``ms_per_step`` -- milliseconds of one timed step (one such call).
+* [--full] ``sustained`` -- the timed loop once more over >= 1 s.
+* [--full] ``replayed_noise`` -- the same call with the recorded ``noise=[z0]`` (rounds 1-2's headline), for comparison.
+* [--full] ``weak_scaling`` (N > 1) -- every rank its own 256 trajectories + the all-gather of N x 256;  ``strong_scaling.global_batch_3200``
   -- the batch the shipped Diffuser pipelines really sample (50 environments x 64 candidate plans) sharded the same way.
-* ``roofline`` prices the single fused kernel against the fp32-MFMA peak using the algorithmic FLOPs of the reference modules
+* [--full] ``roofline`` prices the single fused kernel against the fp32-MFMA peak using the algorithmic FLOPs of the reference modules
   (786.6 MFLOP per trajectory = 39.33 MFLOP x 20 forwards) and the kernel's mean duration from HIP events on the
   launch stream.
-* ``other_configs`` (N = 1) -- the other BASELINE configs and the guided / large-batch variants of config 2, measured by the same
+* [--full] ``predicted_scaling``, ``other_configs`` (N = 1) -- the other BASELINE configs and the guided / large-batch variants of config 2, measured by the same
   process right after the headline (short runs; builder-independent numbers for configs 1, 3, 4, 5).
-* ``cpu_baseline`` (N = 1) -- the imported reference classes when /root/reference is mounted (``kind: "reference"``; build
+* [--full] ``cpu_baseline`` (N = 1) -- the imported reference classes when the reference tree is importable (``kind: "reference"``; build
   container), else the CPU oracle port (oracle/torch_port.py, the same ATen ops the reference runs; ``kind: "port"``; GPU boxes) on
   this host: at the fastest thread count of a probe and at ONE thread, with the CPU model and torch build; plus the recorded figure
   of the real reference measured in the build container (profiles/r04_reference_cpu.json, re-measured per round by tools/measure_reference_cpu.py).  Reported baseline only.
@@ -442,11 +449,18 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=400)      # ~5.6 ms per call: a >= 2 s timed region
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: sustained / replayed-noise loops, scaling legs, roofline, "
+                         "other configs, CPU baseline (the --no-* options below trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 --pmc passes (roofline.traffic then quotes the committed record)")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if args.cpu_baseline_only:               # child process of the N=1 run: CPU oracle timing only
         _, net = build_agent("cpu")
@@ -524,12 +538,66 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    runtime.enable_launch_timing(True)
+    if args.full:
+        runtime.enable_launch_timing(True)
+    # the initial draws of the timed steps come from the global RNG: seeded here, after the warm-up, so that the last step's inputs
+    # depend on the arguments alone (--dump-outputs compares builds output for output)
+    torch.manual_seed(20240 + rank)
     elapsed, x = timed_loop(step, args.steps, 0)
-    kernel_ms = runtime.drain_launch_timing()
-    repair_ms = runtime.drain_repair_timing()
-    runtime.enable_launch_timing(False)
+    if args.full:
+        kernel_ms = runtime.drain_launch_timing()
+        repair_ms = runtime.drain_repair_timing()
+        runtime.enable_launch_timing(False)
     assert torch.isfinite(x).all() and x.shape[0] == BATCH
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "x.npy"), x.detach().float().cpu().numpy())
+
+    line = None
+    if rank == 0:
+        out = {
+            "metric": "denoised trajectories/sec @ (B=256,H=32,D=23) 20-step DDIM",
+            "value": BATCH * args.steps / elapsed,
+            "unit": "trajectories/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": 1e3 * elapsed / args.steps,
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None,     # (the global batch of the metric is fixed: 256 at every N)
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "BASELINE configs[1]: JannerUNet1d Diffuser H=32 D=23, 20-step DDIM, "
+                                   f"global B={BATCH}, whole DiscreteDiffusionSDE.sample() call as a pipeline makes it (initial draw inside)"
+                                   + (f", sharded {BATCH}/{world} per GPU, then one RCCL all-gather of the result" if dist is not None else ""),
+                       "batch_per_gpu": BATCH // world, "global_batch": BATCH, "horizon": HORIZON, "dim": DIM,
+                       "sample_steps": SAMPLE_STEPS, "world_size": world,
+                       "parallelism": f"batch-sharded x{world}; the only data-path collective is the all-gather of the result"},
+        }
+        line = json.dumps(out)
+    if args.full:
+        line = full_measurements(args, out if rank == 0 else None, step=step, step_replayed=step_replayed, step_weak=step_weak,
+                                 timed_loop=timed_loop, agent=agent, device=device, dist=dist, world=world, rank=rank,
+                                 elapsed=elapsed, kernel_ms=kernel_ms, repair_ms=repair_ms, skw=skw)
+    faulthandler.cancel_dump_traceback_later()
+
+    if dist is not None:
+        dist.barrier()
+        dist.destroy_process_group()
+    # The JSON line is the LAST thing this process writes to stdout: RCCL prints a version banner through C stdio, which is
+    # block-buffered on a pipe and would otherwise surface after the line when the process exits.
+    import ctypes
+    try:
+        ctypes.CDLL(None).fflush(None)
+    except (OSError, AttributeError):
+        pass
+    sys.stdout.flush()
+    if rank == 0:
+        print(line, flush=True)
+
+
+def full_measurements(args, out, *, step, step_replayed, step_weak, timed_loop, agent, device, dist, world, rank, elapsed, kernel_ms,
+                      repair_ms, skw):
+    """--full: everything besides the headline, measured by the same process right after the timed steps.  `out` is rank 0's headline
+    record (None on the other ranks); returns rank 0's whole JSON line."""
+    from cleandiffuser_amd import distributed as cdist
     # `value` times EXACTLY --steps calls (the contract); with the driver's --steps 20 that is a 74 ms region (VERDICT r4 weak #9c), so
     # the same loop is timed once more over at least one second and reported next to it (`sustained`)
     sus_steps = max(args.steps, int(1.05 / max(elapsed / args.steps, 1e-6)) + 1)
@@ -586,26 +654,11 @@ def main():
               "peak": 34.5, "unit": "TB/s", "weight_bytes_per_workgroup_forward": wbytes,
               "packed_weight_bytes": 4.0 * comp.prog.meta["blob_floats"], "workgroups": n_wg, "mode": route["mode"], "group": route["k"]}
         l2["frac"] = l2["achieved"] / l2["peak"]
-        out = {
-            "metric": "denoised trajectories/sec @ (B=256,H=32,D=23) 20-step DDIM",
-            "value": BATCH * args.steps / elapsed,
-            "unit": "trajectories/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps,
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None,     # (the global batch of the metric is fixed: 256 at every N)
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "BASELINE configs[1]: JannerUNet1d Diffuser H=32 D=23, 20-step DDIM, "
-                                   f"global B={BATCH}, whole DiscreteDiffusionSDE.sample() call as a pipeline makes it (initial draw inside)"
-                                   + (f", sharded {BATCH}/{world} per GPU, then one RCCL all-gather of the result" if dist is not None else ""),
-                       "batch_per_gpu": BATCH // world, "global_batch": BATCH, "horizon": HORIZON, "dim": DIM,
-                       "sample_steps": SAMPLE_STEPS, "world_size": world,
-                       "parallelism": f"batch-sharded x{world}; the only data-path collective is the all-gather of the result"},
-            "roofline": {"bound": "mfma", "achieved": achieved, "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s",
-                         "frac": achieved / PEAK_FP32_MFMA_TFLOPS, **traffic,
-                         "kernel": kname, "kernel_ms": k_ms,
-                         "launches_timed": len(kernel_ms), "flops_per_launch": FLOPS_PER_TRAJ * launch_b, "trajectories_per_launch": launch_b,
-                         "l2_stream": l2},
-        }
+        out["roofline"] = {"bound": "mfma", "achieved": achieved, "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s",
+                           "frac": achieved / PEAK_FP32_MFMA_TFLOPS, **traffic,
+                           "kernel": kname, "kernel_ms": k_ms,
+                           "launches_timed": len(kernel_ms), "flops_per_launch": FLOPS_PER_TRAJ * launch_b, "trajectories_per_launch": launch_b,
+                           "l2_stream": l2}
         out["sustained"] = {"value": BATCH * sus_steps / el_sus, "unit": "trajectories/s", "ms_per_step": 1e3 * el_sus / sus_steps,
                             "steps": sus_steps, "seconds": el_sus, "what": "the timed loop of `value` once more over >= 1 s"}
         out["roofline"]["repair_launch"] = {
@@ -634,22 +687,8 @@ def main():
             out["other_configs"] = other_configs(device)
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_subprocess()
-        line = json.dumps(out)
-    faulthandler.cancel_dump_traceback_later()
-
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
-    # The JSON line is the LAST thing this process writes to stdout: RCCL prints a version banner through C stdio, which is
-    # block-buffered on a pipe and would otherwise surface after the line when the process exits.
-    import ctypes
-    try:
-        ctypes.CDLL(None).fflush(None)
-    except (OSError, AttributeError):
-        pass
-    sys.stdout.flush()
-    if rank == 0:
-        print(line, flush=True)
+        return json.dumps(out)
+    return None
 
 
 if __name__ == "__main__":

@@ -1,5 +1,6 @@
 """Dataset settings nobody wrote a fixture for: seeded random (class, synthetic data set, horizon / stride / path length / discount /
-reward options) through the REAL reference classes (imported from /root/reference; skipped where the tree is absent) and through
+reward options) through the REAL reference classes (what they computed is read from tests/golden/ref_records/, recorded where the
+reference tree is importable: oracle/ref_records.py) and through
 cleandiffuser_amd/dataset: item tables, every constructor array, the normaliser, ``len`` and a handful of items must be IDENTICAL
 (pure data movement: bit-exact); a setting the reference rejects must be rejected with the same exception type.  All fourteen classes of
 the reference's d4rl_mujoco / d4rl_kitchen / d4rl_antmaze / d4rl_maze2d files are in the draw."""
@@ -13,9 +14,7 @@ import torch
 
 import cleandiffuser_amd.dataset as D
 from oracle import dataset_cases as dc
-from oracle import ref_import
-
-pytestmark = pytest.mark.skipif(not ref_import.available(), reason="reference tree not present on this box")
+from oracle import ref_import, ref_records
 
 SEQ = {  # class -> (reference module, data kind)
     "D4RLMuJoCoDataset": ("d4rl_mujoco_dataset", "mujoco"), "DV_D4RLMuJoCoSeqDataset": ("d4rl_mujoco_dataset", "mujoco"),
@@ -109,23 +108,45 @@ def _cmp(a, b, what):
         assert a == b, what
 
 
+def _reference_side(group, cls, mod, data, kw, u):
+    """What the reference computes for one drawn setting (arrays / nested dicts and lists of them): length, normaliser, constructor
+    arrays, item tables, a handful of items and their collated batch.  `u`: four uniforms that pick the probed items."""
+    from torch.utils.data import default_collate
+    ref_import.import_reference()
+    ref_cls = getattr(importlib.import_module(f"cleandiffuser.dataset.{mod}"), cls)
+    want = ref_cls(copy.deepcopy(data), **kw)
+    n = len(want)
+    probe = sorted({0, n - 1, *(int(v * n) for v in u)}) if n > 0 else []
+    if group == "multi":                              # (the reference cannot serve items past the LAST horizon's table)
+        probe = [i for i in probe if i < min(want.len_each_horizon)]
+    out = {"n": n, "probe": np.array(probe, dtype=np.int64), "mean": np.asarray(want.get_normalizer().mean),
+           "std": np.asarray(want.get_normalizer().std), "items": [_flat(want[i]) for i in probe]}
+    if group == "td":
+        out["attrs"] = {k: getattr(want, k).numpy() for k in ("obs", "next_obs", "act", "rew", "tml")}
+    else:
+        out["attrs"] = {k: np.asarray(getattr(want, k)) for k in ("seq_obs", "seq_act", "seq_rew") +
+                        (("seq_val",) if group == "seq" or cls == "MultiHorizonD4RLMuJoCoDataset" else ())}
+        if group == "multi":
+            out["tables"] = [np.array(want.indices[k], dtype=np.int64).reshape(-1, 3) for k in range(len(kw["horizons"]))]
+        else:
+            out["tables"] = [np.array(want.indices, dtype=np.int64).reshape(-1, 3)]
+    if probe:
+        out["collated"] = _flat(default_collate([want[i] for i in probe]))
+    return out
+
+
 @pytest.mark.parametrize("seed", range(10))
 def test_random_dataset_settings_against_the_imported_reference(seed):
-    ref_import.import_reference()
     rng = random.Random(4400 + seed)
     outcomes = []
-    for _ in range(6):
+    for j in range(6):
         group, cls, mod, skw, kw = _draw(rng)
+        u = [rng.random() for _ in range(4)]
         tag = f"{cls} {skw} {kw}"
         data = dc.make_data(skw)
-        ref_cls = getattr(importlib.import_module(f"cleandiffuser.dataset.{mod}"), cls)
         try:
-            want = ref_cls(copy.deepcopy(data), **kw)
-            n = len(want)
-            probe = sorted({0, n - 1, *(rng.randrange(n) for _ in range(4))}) if n > 0 else []
-            if group == "multi":                              # (the reference cannot serve items past the LAST horizon's table)
-                probe = [i for i in probe if i < min(want.len_each_horizon)]
-            want_items = [_flat(want[i]) for i in probe]
+            want = ref_records.result(f"dataset_{seed}_{j}", tag, lambda: _reference_side(group, cls, mod, data, kw, u))
+            n, probe = want["n"], [int(i) for i in want["probe"]]
         except Exception as e:  # noqa: BLE001
             with pytest.raises(type(e)):
                 got = getattr(D, cls)(copy.deepcopy(data), **kw)
@@ -134,24 +155,23 @@ def test_random_dataset_settings_against_the_imported_reference(seed):
             continue
         got = getattr(D, cls)(copy.deepcopy(data), **kw)
         assert len(got) == n, tag
-        _same(got.get_normalizer().mean, want.get_normalizer().mean, tag + ": mean")
-        _same(got.get_normalizer().std, want.get_normalizer().std, tag + ": std")
+        _same(got.get_normalizer().mean, want["mean"], tag + ": mean")
+        _same(got.get_normalizer().std, want["std"], tag + ": std")
         if group == "td":
             for k in ("obs", "next_obs", "act", "rew", "tml"):
-                _same(getattr(got, k).numpy(), getattr(want, k).numpy(), f"{tag}: {k}")
+                _same(getattr(got, k).numpy(), want["attrs"][k], f"{tag}: {k}")
         else:
             for k in ("seq_obs", "seq_act", "seq_rew") + (("seq_val",) if group == "seq" or cls == "MultiHorizonD4RLMuJoCoDataset" else ()):
-                _same(getattr(got, k), getattr(want, k), f"{tag}: {k}")
+                _same(getattr(got, k), want["attrs"][k], f"{tag}: {k}")
             if group == "multi":
                 for k in range(len(kw["horizons"])):
-                    _same(got.indices[k], np.array(want.indices[k], dtype=np.int64).reshape(-1, 3), f"{tag}: table {k}")
+                    _same(got.indices[k], want["tables"][k], f"{tag}: table {k}")
             else:
-                _same(got.indices, np.array(want.indices, dtype=np.int64).reshape(-1, 3), tag + ": item table")
-        for i, w in zip(probe, want_items):
+                _same(got.indices, want["tables"][0], tag + ": item table")
+        for i, w in zip(probe, want["items"]):
             _cmp(_flat(got[i]), w, f"{tag}: item {i}")
         # the resident loader's batch (host tensors here; one gather launch on the device) = the reference's collated items
         if probe:
-            from torch.utils.data import default_collate
             ld = got.loader(len(probe), shuffle=False, drop_last=False, device="cpu")
             idx = torch.tensor(probe)
             if group == "multi":
@@ -161,6 +181,6 @@ def test_random_dataset_settings_against_the_imported_reference(seed):
             else:
                 T = got.seq_obs.shape[1]
                 batch = ld.batch_of(torch.from_numpy((got.indices[probe, 0] * T + got.indices[probe, 1]).astype(np.int32)))
-            _cmp(_flat(batch), _flat(default_collate([want[i] for i in probe])), f"{tag}: loader batch")
+            _cmp(_flat(batch), want["collated"], f"{tag}: loader batch")
         outcomes.append("ok")
     assert outcomes.count("ok") >= 2, outcomes

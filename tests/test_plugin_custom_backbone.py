@@ -2,13 +2,13 @@
 backbone of the reference's tutorial 4 (tutorials/4_customize_your_diffusion_network_backbone.py:19-118) restated -- dropped into the
 solver classes.  The engine has no program for it, so the request must run the host loop on the module itself (CPU here, the device's
 ATen ops on a GPU) and must not be routed into a fused executor by mistake; sample(), loss() and update() must agree with the imported
-reference (build container) under the same weights, draws and seeds."""
+reference (what it computed is read from tests/golden/ref_records/: oracle/ref_records.py) under the same weights, draws and seeds."""
 import numpy as np
 import pytest
 import torch
 import torch.nn as nn
 
-from oracle import cases, ref_import
+from oracle import cases, ref_records
 
 
 def _define(lib_nn_diffusion, lib_nn_condition):
@@ -88,9 +88,9 @@ def test_custom_backbone_runs_the_host_loop_and_not_a_fused_executor(amd_lib, mo
     assert not bigbatch.is_chiunet_gemm(net, 4096, 6, False)             # ... and no GEMM executor claims it
 
 
-@pytest.mark.skipif(not ref_import.available(), reason="reference tree not present on this box")
 def test_custom_backbone_matches_the_reference(amd_lib):
-    want = _run(cases.lib_namespace("reference"), "reference")
+    want = ref_records.result("plugin_custom_backbone", "Mixer(4) + ObsCondition(9), ContinuousDiffusionSDE, sde_dpmsolver++_2M",
+                              lambda: _run(cases.lib_namespace("reference"), "reference"))
     got = _run(amd_lib, "amd")
     assert abs(got["loss"] - want["loss"]) < 1e-5 * max(1.0, abs(want["loss"]))
     np.testing.assert_allclose(got["upd"], want["upd"], rtol=1e-4)

@@ -1,6 +1,6 @@
 """loss() / update() settings nobody wrote a fixture for: seeded random (solver class, denoiser, prediction type, noise schedule, fix mask,
 loss weight, gradient clipping, EMA rate, optimiser parameters, batch) drawn here and run on the CPU through the REAL reference
-(imported from /root/reference; the test skips where the tree is absent) and through this package with the same synthetic weights and
+(what it computed is read from tests/golden/ref_records/, recorded where its tree is importable: oracle/ref_records.py) and through this package with the same synthetic weights and
 the same seeded timestep / noise / label-dropout draws (oracle/train_cases.py:_record): the loss value, three AdamW + EMA updates, the
 clipped-gradient norms and the parameter / EMA checksums must agree to float rounding.  Every denoiser the reference's pipelines
 train is in the draw (reference diffusion/diffusionsde.py:94-141, newedm.py:152-190, ddpm.py:80-112, rectifiedflow.py)."""
@@ -11,9 +11,7 @@ import pytest
 import torch
 
 from cleandiffuser_amd.utils import load_synth
-from oracle import cases, ref_import, train_cases
-
-pytestmark = pytest.mark.skipif(not ref_import.available(), reason="reference tree not present on this box")
+from oracle import cases, ref_records, train_cases
 
 
 def _denoiser(rng):
@@ -90,14 +88,14 @@ def _run(lib, d):
 
 @pytest.mark.parametrize("seed", range(6))
 def test_random_training_settings_against_the_imported_reference(seed, amd_lib):
-    ref = cases.lib_namespace("reference")
     rng = random.Random(9100 + seed)
     seen = []
-    for _ in range(5):
+    for i in range(5):
         d = _draw(rng)
         tag = f"{d['kind']} / {d['name']} / {d['kw']} / mask {d['mask'] is not None} / weight {d['loss_w'] is not None} / B {d['batch']}"
         try:
-            want = _run(ref, d)
+            want = ref_records.result(f"training_{seed}_{i}", tag + f" / seed {d['seed']} / dropout {d['label_dropout']} / k {rng_k[0]}",
+                                      lambda: _run(cases.lib_namespace("reference"), d))
         except Exception as e:  # noqa: BLE001 -- a setting the reference rejects must be rejected here with the same exception type
             with pytest.raises(type(e)):
                 _run(amd_lib, d)
