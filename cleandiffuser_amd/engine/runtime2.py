@@ -13,7 +13,7 @@ import ctypes
 import os
 import warnings
 import weakref
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -77,7 +77,24 @@ class _Compiled2:
         self.ops_dev = None if prog is None else torch.from_numpy(prog.ops_buffer.copy()).to(prog.blob.device)
 
 
-_cache = weakref.WeakKeyDictionary()
+_cache = weakref.WeakKeyDictionary()       # owner module -> {key: _Compiled2}: every program compiled from its weights
+
+
+def _compiled(owner, key, sig, compile_fn, *args) -> _Compiled2:
+    """The program ``compile_fn(*args)`` compiles for (`owner`, `key`), kept until the weight signature `sig` changes -- then replaced,
+    not added to.  A ValueError of the compiler (the documented 'does not fit / unsupported layer' signal) gives ``.prog is None`` +
+    ``.why``; any other exception (an invariant failure) propagates.  Each key starts with a tag for the kind of program."""
+    per = _cache.setdefault(owner, {})
+    hit = per.get(key)
+    if hit is not None and hit.sig == sig:
+        return hit
+    with torch.no_grad():
+        try:
+            comp = _Compiled2(compile_fn(*args), sig)
+        except ValueError as e:
+            comp = _Compiled2(None, sig, str(e))
+    per[key] = comp
+    return comp
 
 
 def enabled() -> bool:
@@ -88,28 +105,21 @@ def compiled2(module, horizon: int, nw: int = P2.NW2, compact: bool = False) -> 
     """The module's v2 program at this horizon for `nw` waves per workgroup (``.prog is None`` + ``.why`` when the v2 compiler
     does not take it).  `compact`: the small-LDS variant that lets three trajectories share a workgroup (state and multistep memory
     in global memory, in-place residual outputs, capped staging area) -- a third of 160 KiB or it does not exist."""
-    per_mod = _cache.setdefault(module, {})
-    sig = R._signature(module)
-    key = (horizon, nw, bool(compact))
-    hit = per_mod.get(key)
-    if hit is not None and hit.sig == sig:
-        return hit
-    with torch.no_grad():
-        try:
-            kw = dict(compact=True, max_stage=COMPACT_STAGE, max_lds_bytes=(160 * 1024) // 3 // 16 * 16) if compact else {}
-            lower = P2.compile_chiunet2 if R._is_chiunet(module) else P2.compile_janner2
-            try:
-                comp = _Compiled2(lower(module, horizon, nw=nw, **kw), sig)
-            except ValueError:
-                if compact or nw != P2.NW2_MAX or os.environ.get("CDX_UNET2_COMPACT_T1", "1") == "0":
-                    raise
-                # nets whose default plan does not fit 160 KiB (model_dim 64 at H = 64: the antmaze Diffuser, 193 KB) may still fit as
-                # a compact program with the whole LDS to itself: one trajectory per workgroup
-                comp = _Compiled2(lower(module, horizon, nw=nw, compact=True), sig)
-        except ValueError as e:                  # the documented 'does not fit / unsupported layer' signal; invariant failures propagate
-            comp = _Compiled2(None, sig, str(e))
-    per_mod[key] = comp
-    return comp
+    return _compiled(module, ("unet", horizon, nw, bool(compact)), R._signature(module), _compile_unet2, module, horizon, nw, compact)
+
+
+def _compile_unet2(module, horizon: int, nw: int, compact: bool) -> P2.Program2:
+    lower = P2.compile_chiunet2 if R._is_chiunet(module) else P2.compile_janner2
+    if compact:
+        return lower(module, horizon, nw=nw, compact=True, max_stage=COMPACT_STAGE, max_lds_bytes=(160 * 1024) // 3 // 16 * 16)
+    try:
+        return lower(module, horizon, nw=nw)
+    except ValueError:
+        if nw != P2.NW2_MAX or os.environ.get("CDX_UNET2_COMPACT_T1", "1") == "0":
+            raise
+        # nets whose default plan does not fit 160 KiB (model_dim 64 at H = 64: the antmaze Diffuser, 193 KB) may still fit as a
+        # compact program with the whole LDS to itself: one trajectory per workgroup
+        return lower(module, horizon, nw=nw, compact=True)
 
 
 COMPACT_STAGE = 2304       # floats of staging area per op in a compact program
@@ -442,6 +452,11 @@ def whole_chip(device) -> bool:
 
 last_exchange_error = {}    # device -> what the first member that gave up reported (diagnostics; see check_split_errors)
 _split_errs = {}     # device -> one int32 in PINNED HOST memory: a member that loses a granule writes 1 there (over PCIe, on failure only)
+_split_ok = {}       # device -> did the small-batch mode pass its first-use check there (absent: not checked yet)
+_group_ok = {}       # ... the full-batch grouped mode
+_sguided_ok = {}     # ... the small-batch (split) GUIDED mode
+_gguided_ok = {}     # ... the grouped GUIDED mode
+_MODE_FLAGS = {(False, False): _split_ok, (True, False): _group_ok, (False, True): _sguided_ok, (True, True): _gguided_ok}  # (group, guided)
 
 
 def _split_err(device) -> torch.Tensor:
@@ -458,19 +473,26 @@ def _report_of(word) -> dict:
             "group": grp}
 
 
+def _modes_off(device, word) -> None:
+    """Every split / grouped mode, unguided and guided, off for `device` for the rest of the process (its workgroups are evidently not
+    co-resident behind one L2), with the first report of the error word `word`."""
+    for ok in _MODE_FLAGS.values():
+        ok[device] = False
+    last_exchange_error[device] = _report_of(word)
+
+
 def note_exchange_failure(device) -> bool:
-    """Has a split / grouped launch on `device` reported a lost granule (so far -- no synchronisation)?  If so both modes go off for the
-    device for the rest of the process (its workgroups are evidently not co-resident behind one L2) and a warning says why.  The error
-    word is NOT cleared here: repair launches that are still queued behind earlier split / grouped launches read it (cdx.h: run_if), and
-    with the modes off nothing will raise it again.  Looking costs nothing (a numpy view of pinned host memory)."""
+    """Has a split / grouped launch on `device` reported a lost granule (so far -- no synchronisation)?  If so every split / grouped mode
+    goes off for the device (_modes_off) and a warning says why, once.  The error word is NOT cleared here: repair launches that are still
+    queued behind earlier split / grouped launches read it (cdx.h: run_if), and with the modes off nothing will raise it again.  Looking
+    costs nothing (a numpy view of pinned host memory)."""
     ent = _split_errs.get(device)
     if ent is None or int(ent[1][0]) == 0:
         return False
-    if _split_ok.get(device) is not False or _group_ok.get(device) is not False:
-        _split_ok[device] = _group_ok[device] = _gguided_ok[device] = _sguided_ok[device] = False
-        last_exchange_error[device] = _report_of(ent[1])
+    if any(ok.get(device) is not False for ok in _MODE_FLAGS.values()):
+        _modes_off(device, ent[1])
         warnings.warn("cdx_unet2_run (split / grouped program): a member never received a granule; the affected request was recomputed by "
-                      "the ordinary program on the same stream (repair launch), and both modes are now off for this device "
+                      "the ordinary program on the same stream (repair launch), and the split / grouped modes are now off for this device "
                       f"(first report: {last_exchange_error[device]})")
     return True
 
@@ -479,20 +501,19 @@ def check_split_errors(device=None, wait: bool = True):
     """Raise if a split / grouped launch lost a granule (its polls are bounded: the launch ends; the workgroup that gave up stored NaN
     instead of its trajectories -- which the REPAIR launch behind it then overwrote with the ordinary program's result, so a caller of
     sample() never sees them).  `wait=True` (tests, explicit calls) synchronises the device first and clears the error word -- nothing
-    is in flight then; `wait=False` only looks.  A device on which this fires loses both modes for the rest of the process."""
+    is in flight then; `wait=False` only looks.  A device on which this fires loses every split / grouped mode (_modes_off)."""
     for dev, (_, word) in list(_split_errs.items()):
         if device is not None and dev != device:
             continue
         if wait:
             torch.cuda.synchronize(dev)
         if int(word[0]) != 0:
-            _split_ok[dev] = _group_ok[dev] = _gguided_ok[dev] = _sguided_ok[dev] = False
-            last_exchange_error[dev] = _report_of(word)
+            _modes_off(dev, word)
             if wait:
                 word[:] = 0
             raise RuntimeError("cdx_unet2_run (split / grouped program): a member never received a granule; the trajectories of that "
-                               "launch were recomputed by the repair launch behind it, and both modes are now off for this device "
-                               f"(first report: {last_exchange_error[dev]})")
+                               "launch were recomputed by the repair launch behind it, and the split / grouped modes are now off for this "
+                               f"device (first report: {last_exchange_error[dev]})")
 
 
 def group_placement(device=None) -> dict:
@@ -544,40 +565,12 @@ def group_factor(batch: int) -> int:
     return 1
 
 
-_scache = weakref.WeakKeyDictionary()
-_gcache2 = weakref.WeakKeyDictionary()
-
-
 def compiled_group2(module, horizon: int, k: int) -> _Compiled2:
-    per = _gcache2.setdefault(module, {})
-    sig = R._signature(module)
-    key = (horizon, k, P2.group_min_bytes())
-    hit = per.get(key)
-    if hit is not None and hit.sig == sig:
-        return hit
-    with torch.no_grad():
-        try:
-            comp = _Compiled2(P2.compile_janner2_group(module, horizon, k), sig)
-        except ValueError as e:
-            comp = _Compiled2(None, sig, str(e))
-    per[key] = comp
-    return comp
-
+    return _compiled(module, ("group", horizon, k, P2.group_min_bytes()), R._signature(module), P2.compile_janner2_group, module, horizon, k)
 
 
 def compiled_split2(module, horizon: int, k: int) -> _Compiled2:
-    per = _scache.setdefault(module, {})
-    sig = R._signature(module)
-    hit = per.get((horizon, k))
-    if hit is not None and hit.sig == sig:
-        return hit
-    with torch.no_grad():
-        try:
-            comp = _Compiled2(P2.compile_janner2_split(module, horizon, k), sig)
-        except ValueError as e:
-            comp = _Compiled2(None, sig, str(e))
-    per[(horizon, k)] = comp
-    return comp
+    return _compiled(module, ("split", horizon, k), R._signature(module), P2.compile_janner2_split, module, horizon, k)
 
 
 _emb_bufs = {}
@@ -678,23 +671,9 @@ def fused_sample2(solver, net, plan, xt, prior, feed, fix_mask, x_min, x_max, x_
         return None
     dev = xt.device
     comp, parts = plan_for(net, h, b)
-    split, plain, group = 0, None, False
-    # (split / grouped launches carry per-launch sequence numbers and ticket bases as kernel arguments: a captured launch would replay
-    #  stale ones -- under stream capture the ordinary program serves the request)
-    capturing = dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
-    if not chi and not use_cond and not edm and not comp.prog.compact and not capturing and \
-            (R._prof["buf"] is None or os.environ.get("CDX_UNET2_GROUP_PROF") == "1") and _modes_allowed(dev):
-        k = split_factor(b) if _split_ok.get(dev, True) and R._prof["buf"] is None else 1      # small batches: one trajectory over k workgroups of an XCD
-        if k > 1:
-            alt = compiled_split2(net, h, k)
-            if alt.prog is not None:
-                plain, (comp, parts, split) = (comp, parts), (alt, None, k)
-        elif _group_ok.get(dev, True):
-            k = group_factor(b)                       # one trajectory per CU: k trajectories over the k workgroups of a group
-            if k > 1:
-                alt = compiled_group2(net, h, k)
-                if alt.prog is not None:
-                    plain, (comp, parts, split, group) = (comp, parts), (alt, None, k, True)
+    route = None
+    if not chi and not use_cond and not edm and not comp.prog.compact:
+        route = member_route(net, h, b, dev, dev.type == "cuda" and torch.cuda.is_current_stream_capturing())
     if chi:
         cond = torch.flatten(cond, 1)
         if cond.shape != (b, comp.prog.meta["cond_dim"]):
@@ -712,50 +691,19 @@ def fused_sample2(solver, net, plan, xt, prior, feed, fix_mask, x_min, x_max, x_
             emb = cond_film_table(comp, net, R.device_times(plan, dev), R._f32c(cond, dev))
             if w_cfg != 1.0:
                 emb_u = plan_film_table(comp, net, plan, dev)                 # zero condition: the per-step table
-        else:
-            emb = plan_film_table(comp, net, plan, dev)
+        else:       # (a member program's own table: its repair / check launches on the ordinary program read it as well)
+            emb = plan_film_table(comp if route is None else route.comp, net, plan, dev)
         noise = feed.many(xt, plan.n_noise)
         xin = R._f32c(xt, dev)
         out = torch.empty_like(xin)
         kw = dict(batch=b, x_in=xin, emb=emb, steps_dev=steps_dev, n_steps=len(plan.steps), predict_noise=R._predicts_noise(plan, solver),
                   prior=R._f32c(prior, dev) if fix_mask is not None else None, fix_mask=fix_mask, noise=noise, x_min=x_min, x_max=x_max,
                   x_scale=x_scale, emb_per_traj=use_cond, emb_u=emb_u, cfg_w=w_cfg, edm=edm)
-        launch(comp, x_out=out, parts=parts, split=split, group=group, t_per_wg=1 if split else None, **kw)
-        if split and _repair_on():
-            # REPAIR launch: the same request on the ordinary program, gated on the error word of the launch above (cdx.h: run_if).  Stream
-            # order puts it between that launch and every consumer of `out`: a lost granule (bounded polls -> NaN trajectories) is
-            # recomputed before anybody can observe it; when nothing failed every workgroup returns at once (~10 us of a 3.6 ms call).
-            launch(plain[0], x_out=out, parts=plain[1], run_if=_split_err(dev), **kw)
-        ok = _group_ok if group else _split_ok
-        if split and dev not in ok:
-            # First split / grouped launch on this device: checked ONCE against the ordinary program on this very request -- a dispatcher
-            # that does not give the launch one workgroup per CU shows up as a lost granule or as different numbers, and the mode stays
-            # off for the process instead of failing later.
-            ref = torch.empty_like(xin)
-            launch(plain[0], x_out=ref, parts=plain[1], **kw)
-            try:
-                check_split_errors(dev, wait=True)
-                good = bool(torch.allclose(out, ref, rtol=1e-3, atol=1e-3))
-            except RuntimeError as e:
-                warnings.warn(f"first-use check of the {'grouped' if group else 'small-batch'} mode: {e}")
-                good = False
-            ok[dev] = good
-            if not good:
-                return ref
-        elif split and _sync_check(group):
-            # CDX_UNET2_SPLIT_SYNC=1: look at the error word of THIS launch before the call returns (the mode then switches off one call
-            # earlier).  Not needed for safety any more -- the repair launch has already replaced a failed result.
-            torch.cuda.current_stream(dev).synchronize()
-            note_exchange_failure(dev)
+        if route is None:
+            launch(comp, x_out=out, parts=parts, split=0, group=False, **kw)
+        else:
+            out = _launch_members(dev, route, kw, comp, kw, {"x_out": out}, parts=parts)["x_out"]
     return out
-
-
-def _sync_check(group: bool) -> bool:
-    return os.environ.get("CDX_UNET2_SPLIT_SYNC") == "1"
-
-
-def _repair_on() -> bool:
-    return os.environ.get("CDX_UNET2_REPAIR", "1") != "0"       # (=0: A/B runs that price the repair launch; a failed exchange then hands out NaN)
 
 
 def _modes_allowed(dev) -> bool:
@@ -766,8 +714,73 @@ def _modes_allowed(dev) -> bool:
     return whole_chip(dev)
 
 
-_split_ok = {}       # device -> did the small-batch mode pass its one-time check there (absent: not checked yet)
-_group_ok = {}       # ... the full-batch grouped mode
+class Route(NamedTuple):
+    """A split / grouped launch: `mode` "split" (one trajectory over k workgroups of an XCD) or "grouped" (k trajectories over the k
+    workgroups of a group), the member program, and whether it is the guided variant."""
+    mode: str
+    k: int
+    comp: _Compiled2
+    guided: bool
+
+    @property
+    def group(self) -> bool:
+        return self.mode == "grouped"
+
+
+def member_route(net, horizon: int, batch: int, dev, capturing: bool, clf_net=None) -> Optional[Route]:
+    """Split, grouped or neither (None) for a request of `batch` trajectories on `dev`: the one answer fused_sample2, guided_sample2
+    (`clf_net`: the classifier of a guided request) and route_info act on.  The gates held here: a whole MI355X and no lost granule so
+    far (_modes_allowed); no stream capture (`capturing`: split / grouped launches carry per-launch sequence numbers and ticket bases as
+    kernel arguments, a captured launch would replay stale ones); no profile buffer, except for the unguided grouped program under
+    CDX_UNET2_GROUP_PROF=1 (tools/op_profile2.py); the mode's own flag and switch; its factor.  Small-batch split first, then grouped
+    (with the default factors their batch ranges do not overlap): the first mode whose factor exceeds 1 decides, None when its program
+    does not exist.  The gates of the request itself (conditioning, EDM, compact or forced shapes, ...) stay with the callers."""
+    if capturing or not _modes_allowed(dev):
+        return None
+    guided, prof = clf_net is not None, R._prof["buf"] is not None
+    for group in (False, True):
+        if prof and (guided or not group or os.environ.get("CDX_UNET2_GROUP_PROF") != "1"):
+            continue
+        if not _MODE_FLAGS[group, guided].get(dev, True):
+            continue
+        if guided and os.environ.get("CDX_UNET2_GUIDED_GROUP" if group else "CDX_UNET2_GUIDED_SPLIT", "1") == "0":
+            continue
+        k = group_factor(batch) if group else split_factor(batch)
+        if k > 1:
+            if guided:
+                comp = (compiled_guided_group2 if group else compiled_guided_split2)(net, clf_net, horizon, k)
+            else:
+                comp = (compiled_group2 if group else compiled_split2)(net, horizon, k)
+            return Route("grouped" if group else "split", k, comp, guided) if comp.prog is not None else None
+    return None
+
+
+def _launch_members(dev, route: Route, member_kw: dict, plain: _Compiled2, kw: dict, outs: dict, **plain_kw) -> dict:
+    """The launch protocol of a split / grouped request.  `outs`: the output tensors by launch keyword (x_out, and logp_out of a guided
+    request); `member_kw`: every other argument of the member program's launch; `kw` + `plain_kw`: those of the ordinary program
+    `plain`'s.  Returns the outputs to hand out.
+    1. The member launch.
+    2. Its REPAIR launch: the same request on the ordinary program, gated on the device's error word (cdx.h: run_if).  Stream order puts
+       it between the member launch and every consumer of the outputs: a lost granule (bounded polls -> NaN trajectories) is recomputed
+       before anybody can observe it; when nothing failed every workgroup returns at once (~10 us of a 3.6 ms call).
+    3. The mode's first use on this device: checked ONCE against the ordinary program on this very request -- a dispatcher that does not
+       give the launch one workgroup per CU shows up as a lost granule or as different numbers, and the mode stays off for the process
+       (this call hands out the ordinary program's outputs) instead of failing later."""
+    launch(route.comp, split=route.k, group=route.group, t_per_wg=1, **member_kw, **outs)
+    launch(plain, run_if=_split_err(dev), **plain_kw, **kw, **outs)
+    ok = _MODE_FLAGS[route.group, route.guided]
+    if dev in ok:
+        return outs
+    ref = {name: torch.empty_like(t) for name, t in outs.items()}
+    launch(plain, **plain_kw, **kw, **ref)
+    try:
+        check_split_errors(dev, wait=True)
+        good = all(bool(torch.allclose(outs[name], ref[name], rtol=1e-3, atol=1e-3)) for name in outs)
+    except RuntimeError as e:
+        warnings.warn(f"first-use check of the {'grouped' if route.group else 'small-batch'}{' guided' if route.guided else ''} mode: {e}")
+        good = False
+    ok[dev] = good
+    return outs if good else ref
 
 
 def stream_bytes_per_forward(prog: P2.Program2, member: int = 0) -> int:
@@ -781,21 +794,13 @@ def route_info(net, horizon: int, batch: int, device) -> dict:
     """How an unconditional JannerUNet1d sampling loop of `batch` trajectories is launched on `device` right now -- what fused_sample2
     decides, for reporting (bench.py's `roofline`): mode "grouped" (k trajectories over the k workgroups of a group), "split" (one
     trajectory over k workgroups) or "plain"; the program, the launch parts, the number of workgroups and the weight bytes a workgroup
-    streams per forward."""
+    streams per forward.  (An uncaptured call: reporting happens outside stream capture.)"""
     comp, parts = plan_for(net, horizon, batch)
-    mode, k = "plain", 1
-    if not comp.prog.compact and R._prof["buf"] is None:
-        ks = split_factor(batch) if _split_ok.get(device, True) else 1
-        if ks > 1 and compiled_split2(net, horizon, ks).prog is not None:
-            mode, k, comp, parts = "split", ks, compiled_split2(net, horizon, ks), None
-        elif ks == 1 and _group_ok.get(device, True):
-            kg = group_factor(batch)
-            if kg > 1 and compiled_group2(net, horizon, kg).prog is not None:
-                mode, k, comp, parts = "grouped", kg, compiled_group2(net, horizon, kg), None
-    if mode in ("split", "grouped"):
-        n_wg = N_CUS                      # always one workgroup per CU (the groups are formed from per-XCD tickets)
-    else:
-        n_wg = sum(-(-cnt // t) for _, cnt, t in parts)
+    route = None if comp.prog.compact else member_route(net, horizon, batch, torch.device(device), capturing=False)
+    if route is None:
+        mode, k, n_wg = "plain", 1, sum(-(-cnt // t) for _, cnt, t in parts)
+    else:                                 # always one workgroup per CU (the groups are formed from per-XCD tickets)
+        mode, k, comp, parts, n_wg = route.mode, route.k, route.comp, None, N_CUS
     return {"mode": mode, "k": k, "comp": comp, "parts": parts, "workgroups": n_wg,
             "stream_bytes_per_workgroup_forward": stream_bytes_per_forward(comp.prog)}
 
@@ -836,74 +841,45 @@ def backbone_forward2(module, x, noise_t, condition=None) -> Optional[torch.Tens
 # ------------------------------------------------------------------------------------------------------------------- #
 # classifier-guided sampling: denoiser forward + classifier forward/backward in the same launch                          #
 # ------------------------------------------------------------------------------------------------------------------- #
-_gcache = weakref.WeakKeyDictionary()
-
-
 def compiled_guided2(net, clf_net, horizon: int, two: bool = False, three: bool = False) -> _Compiled2:
     """Guided program (denoiser ops, then the HalfJannerUNet1d classifier's forward and backward-data ops), 8-wave shape.  `two`: the
     variant for two trajectories per workgroup -- saved tensors in a global workspace, small staging area.  ``.prog is None`` +
     ``.why`` when it does not exist (LDS plan, unsupported layers)."""
-    per = _gcache.setdefault(net, {})
-    sig = (R._signature(net), R._signature(clf_net))
-    key = (id(clf_net), horizon, bool(two), bool(three))
-    hit = per.get(key)
-    if hit is not None and hit.sig == sig:
-        return hit
-    with torch.no_grad():
+    return _compiled(net, ("guided", id(clf_net), horizon, bool(two), bool(three)), (R._signature(net), R._signature(clf_net)),
+                     _compile_guided2, net, clf_net, horizon, two, three)
+
+
+def _compile_guided2(net, clf_net, horizon: int, two: bool, three: bool) -> P2.Program2:
+    if three:            # compact on top: state / multistep memory in global memory, in-place residual outputs (config 2: 49.6 KB)
+        return P2.compile_guided2(net, clf_net, horizon, save_global=True, compact=True, max_stage=GUIDED_T2_STAGE,
+                                  max_lds_bytes=(160 * 1024) // 3 // 16 * 16)
+    if two:
+        return P2.compile_guided2(net, clf_net, horizon, save_global=True, max_stage=GUIDED_T2_STAGE, max_lds_bytes=80 * 1024)
+    try:
+        return P2.compile_guided2(net, clf_net, horizon)
+    except ValueError:                               # (LDS plan too large)
+        # wider nets, one trajectory per workgroup: saved tensors in the global workspace (model_dim 64 at H = 32, the kitchen
+        # Diffuser: 141 KB), then also the state / multistep memory in global memory and in-place residual outputs (model_dim
+        # 64 at H = 64, the antmaze Diffuser: 158 KB)
         try:
-            kw = dict(save_global=True, max_stage=GUIDED_T2_STAGE, max_lds_bytes=80 * 1024) if two else {}
-            if three:        # compact on top: state / multistep memory in global memory, in-place residual outputs (config 2: 49.6 KB)
-                kw = dict(save_global=True, compact=True, max_stage=GUIDED_T2_STAGE, max_lds_bytes=(160 * 1024) // 3 // 16 * 16)
-            try:
-                comp = _Compiled2(P2.compile_guided2(net, clf_net, horizon, **kw), sig)
-            except ValueError:                           # (LDS plan too large)
-                if two or three:
-                    raise
-                # wider nets, one trajectory per workgroup: saved tensors in the global workspace (model_dim 64 at H = 32, the kitchen
-                # Diffuser: 141 KB), then also the state / multistep memory in global memory and in-place residual outputs (model_dim
-                # 64 at H = 64, the antmaze Diffuser: 158 KB)
-                try:
-                    comp = _Compiled2(P2.compile_guided2(net, clf_net, horizon, save_global=True), sig)
-                except ValueError:
-                    comp = _Compiled2(P2.compile_guided2(net, clf_net, horizon, save_global=True, compact=True), sig)
-        except ValueError as e:
-            comp = _Compiled2(None, sig, str(e))
-    per[key] = comp
-    return comp
-
-
-_ggcache = weakref.WeakKeyDictionary()
-_gguided_ok = {}     # device -> did the grouped GUIDED mode pass its one-time check there (absent: not checked yet)
-_sguided_ok = {}     # ... the small-batch (split) GUIDED mode
+            return P2.compile_guided2(net, clf_net, horizon, save_global=True)
+        except ValueError:
+            return P2.compile_guided2(net, clf_net, horizon, save_global=True, compact=True)
 
 
 def compiled_guided_group2(net, clf_net, horizon: int, k: int) -> _Compiled2:
     """The GROUPED guided program (P2.compile_guided2_group): the denoiser's stream-bound layers computed per member for 1/k of the output
     channels of the group's k trajectories, everything else -- the classifier's forward / backward ops included -- on the member's own
     trajectory.  ``.prog is None`` + ``.why`` when it does not exist."""
-    return _compiled_guided_members(net, clf_net, horizon, k, True)
+    return _compiled(net, ("guided_group", id(clf_net), horizon, k, P2.group_min_bytes()), (R._signature(net), R._signature(clf_net)),
+                     P2.compile_guided2_group, net, clf_net, horizon, k)
 
 
 def compiled_guided_split2(net, clf_net, horizon: int, k: int) -> _Compiled2:
     """The SMALL-BATCH guided program (P2.compile_guided2_split): one trajectory over k workgroups of an XCD, the denoiser's ops cut by
     row tiles where that pays, the classifier's ops computed by every member."""
-    return _compiled_guided_members(net, clf_net, horizon, k, False)
-
-
-def _compiled_guided_members(net, clf_net, horizon: int, k: int, group: bool) -> _Compiled2:
-    per = _ggcache.setdefault(net, {})
-    sig = (R._signature(net), R._signature(clf_net))
-    key = (id(clf_net), horizon, k, group, P2.group_min_bytes())
-    hit = per.get(key)
-    if hit is not None and hit.sig == sig:
-        return hit
-    with torch.no_grad():
-        try:
-            comp = _Compiled2((P2.compile_guided2_group if group else P2.compile_guided2_split)(net, clf_net, horizon, k), sig)
-        except ValueError as e:
-            comp = _Compiled2(None, sig, str(e))
-    per[key] = comp
-    return comp
+    return _compiled(net, ("guided_split", id(clf_net), horizon, k, P2.group_min_bytes()), (R._signature(net), R._signature(clf_net)),
+                     P2.compile_guided2_split, net, clf_net, horizon, k)
 
 
 GUIDED_T2_STAGE = 2304       # floats of staging area a two-trajectory guided program may use per op (config 2: 2 x 80.8 KB of LDS)
@@ -959,47 +935,18 @@ def guided_sample2(solver, net, clf_net, plan, xt, prior, feed, fix_mask, x_min,
         kw = dict(batch=b, x_in=xin, emb=emb, steps_dev=steps_dev, n_steps=len(plan.steps), predict_noise=pn,
                   prior=R._f32c(prior, dev) if fix_mask is not None else None, fix_mask=fix_mask, noise=noise, x_min=x_min,
                   x_max=x_max, cg_scale=cg)
-        # GROUPED guided launch (round 6): one trajectory per CU, groups of k workgroups share the weight stream of the denoiser's
-        # stream-bound layers -- the unguided grouped mode (`sample2`) with the classifier's ops on each member's own trajectory; same
-        # gates (whole chip, no capture, no lost granule so far), same repair launch, same one-time check against the ordinary program
-        # ... and below 129 trajectories the SMALL-BATCH form: one trajectory over 2 or 4 workgroups, the denoiser's ops cut by row tiles
-        # (`compile_guided2_split`), the classifier's ops computed by every member (CDX_UNET2_GUIDED_SPLIT=0: off)
-        gk, galt, ggroup = 1, None, True
-        capturing = dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
-        if forced is None and t == 1 and parts is None and with_logp and not capturing and R._prof["buf"] is None and _modes_allowed(dev):
-            if os.environ.get("CDX_UNET2_GUIDED_GROUP", "1") != "0" and _gguided_ok.get(dev, True):
-                gk = group_factor(b)
-                if gk > 1:
-                    galt = compiled_guided_group2(net, clf_net, h, gk)
-            if galt is None and os.environ.get("CDX_UNET2_GUIDED_SPLIT", "1") != "0" and _sguided_ok.get(dev, True):
-                gk = split_factor(b)
-                if gk > 1:
-                    galt, ggroup = compiled_guided_split2(net, clf_net, h, gk), False
-            if galt is not None and galt.prog is None:
-                gk, galt = 1, None
-        if galt is not None:
-            ok_map = _gguided_ok if ggroup else _sguided_ok
-            gemb = plan_film_table(galt, net, plan, dev, modules=[net, clf_net], zero_row=with_logp)
-            launch(galt, x_out=out, t_per_wg=1, split=gk, group=ggroup, logp_out=logp, **{**kw, "emb": gemb})
-            if _repair_on():
-                launch(comp, x_out=out, t_per_wg=t, logp_out=logp, run_if=_split_err(dev), **kw)
-            if dev not in ok_map:
-                ref, ref_logp = torch.empty_like(xin), torch.empty_like(logp)
-                launch(comp, x_out=ref, t_per_wg=t, logp_out=ref_logp, **kw)
-                try:
-                    check_split_errors(dev, wait=True)
-                    good = bool(torch.allclose(out, ref, rtol=1e-3, atol=1e-3)) and bool(torch.allclose(logp, ref_logp, rtol=1e-3, atol=1e-3))
-                except RuntimeError as e:
-                    warnings.warn(f"first-use check of the {'grouped' if ggroup else 'small-batch'} guided mode: {e}")
-                    good = False
-                ok_map[dev] = good
-                if not good:
-                    out, logp = ref, ref_logp
-            elif _sync_check(True):
-                torch.cuda.current_stream(dev).synchronize()
-                note_exchange_failure(dev)
-        else:
+        # the guided member modes (round 6): at 128 < B <= 256 GROUPED -- groups of k workgroups share the weight stream of the denoiser's
+        # stream-bound layers, the classifier's ops run on each member's own trajectory; below 129 trajectories SMALL-BATCH -- one
+        # trajectory over 2 or 4 workgroups, the denoiser's ops cut by row tiles, the classifier's ops computed by every member
+        route = None
+        if forced is None and t == 1 and parts is None and with_logp:
+            route = member_route(net, h, b, dev, dev.type == "cuda" and torch.cuda.is_current_stream_capturing(), clf_net)
+        if route is None:
             launch(comp, x_out=out, t_per_wg=t, parts=parts, logp_out=logp, **kw)
+        else:
+            gemb = plan_film_table(route.comp, net, plan, dev, modules=[net, clf_net], zero_row=with_logp)
+            res = _launch_members(dev, route, {**kw, "emb": gemb}, comp, kw, {"x_out": out, "logp_out": logp}, t_per_wg=t)
+            out, logp = res["x_out"], res["logp_out"]
         if logp is not None:
             # the classifier's score of the FINAL trajectories (timestep 0) came out of the same launch: handed to the solver's
             # post-processing on the tensor itself (diffusionsde._sample_common reads it instead of calling classifier.logp)
@@ -1021,24 +968,10 @@ def classifier_gradient2(net, clf_net, x, noise_t) -> Optional[torch.Tensor]:
     return out
 
 
-_ccache = weakref.WeakKeyDictionary()
-
-
 def compiled_classifier2(clf_net, horizon: int) -> _Compiled2:
     """The classifier's own program (forward ops + head, engine/program2.py:compile_classifier2); ``.prog is None`` + ``.why`` when
     the v2 compiler does not take it."""
-    per = _ccache.setdefault(clf_net, {})
-    sig = R._signature(clf_net)
-    hit = per.get(horizon)
-    if hit is not None and hit.sig == sig:
-        return hit
-    with torch.no_grad():
-        try:
-            comp = _Compiled2(P2.compile_classifier2(clf_net, horizon), sig)
-        except ValueError as e:
-            comp = _Compiled2(None, sig, str(e))
-    per[horizon] = comp
-    return comp
+    return _compiled(clf_net, ("classifier", horizon), R._signature(clf_net), P2.compile_classifier2, clf_net, horizon)
 
 
 def classifier_forward2(clf_net, x, noise_t) -> Optional[torch.Tensor]:
@@ -1069,22 +1002,9 @@ def classifier_forward2(clf_net, x, noise_t) -> Optional[torch.Tensor]:
 # ------------------------------------------------------------------------------------------------------------------- #
 # batch-tiled MLP denoisers (PearceMlp, DQLMlp / DVInvMlp, MlpNNDiffusion, SfBCUNet) on the second-generation kernel     #
 # ------------------------------------------------------------------------------------------------------------------- #
-_mcache = weakref.WeakKeyDictionary()
-
-
 def compiled_mlp2(net, kind: str, tile: int) -> _Compiled2:
-    per = _mcache.setdefault(net, {})
-    sig = R._signature(net)
-    hit = per.get(tile)
-    if hit is not None and hit.sig == sig:
-        return hit
-    with torch.no_grad():
-        try:
-            comp = _Compiled2(P2.MLP2_COMPILERS[kind](net, tile), sig)
-        except ValueError as e:                        # widths the epilogue partition / GroupNorm layout does not take (the
-            comp = _Compiled2(None, sig, str(e))        #  documented signal; invariant failures of the compiler propagate)
-    per[tile] = comp
-    return comp
+    # (.prog is None: widths the epilogue partition / GroupNorm layout does not take)
+    return _compiled(net, ("mlp", tile), R._signature(net), P2.MLP2_COMPILERS[kind], net, tile)
 
 
 def mlp_table(comp: _Compiled2, net, plan, device) -> torch.Tensor:

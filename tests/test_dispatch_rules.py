@@ -1,6 +1,8 @@
 """Host-side routing rules between the two native U-Net executors and the PyTorch executor (engine/dispatch.py, bigbatch.py,
 runtime.py) -- pure Python decisions, checked on the CPU."""
 import os
+
+import pytest
 import torch
 
 from cleandiffuser_amd.engine import bigbatch, plan as P, runtime, runtime2
@@ -87,6 +89,75 @@ def test_standalone_forward_of_a_v2_net_keeps_the_gemm_crossover():
     assert not bigbatch.is_chiunet_gemm(net, 3200, 32)                       # loop: v2 program kernel
     assert bigbatch.is_chiunet_gemm(net, 3200, 32, forward=True)             # forward at the Diffuser batch: GEMM executor
     assert not bigbatch.is_chiunet_gemm(net, 256, 32, forward=True)
+
+
+def test_member_mode_route_table(monkeypatch):
+    """runtime2.member_route: the one answer "split, grouped or neither, and with what k" that fused_sample2, guided_sample2 and route_info
+    act on.  Config 2 at H = 32 on a whole chip, guided and unguided alike: small-batch split at k = 4 up to 64 trajectories and k = 2 up
+    to 128, grouped at k = 4 up to 256, neither above.  An ok-flag that is off removes its own mode only; stream capture or a profile
+    buffer gives neither; so does a device whole_chip() refuses -- where route_info reports the ordinary program fused_sample2 runs."""
+    from cleandiffuser_amd.nn_classifier import HalfJannerUNet1d
+    for name in ("CDX_UNET2_SPLIT", "CDX_UNET2_GROUP", "CDX_UNET2_GUIDED_SPLIT", "CDX_UNET2_GUIDED_GROUP", "CDX_UNET2_T", "CDX_UNET2_NW",
+                 "CDX_UNET2_GROUP_PROF"):
+        monkeypatch.delenv(name, raising=False)
+    monkeypatch.setenv("CDX_UNET2_ASSUME_WHOLE_CHIP", "1")
+    net = JannerUNet1d(23, model_dim=32, emb_dim=32, dim_mult=[1, 2, 2, 2], kernel_size=5)
+    clf = HalfJannerUNet1d(32, 23, out_dim=1, model_dim=32, emb_dim=32, dim_mult=(1, 2, 2, 2), kernel_size=3)
+    dev = torch.device("cuda", 0)
+    flags = {(False, None): runtime2._split_ok, (True, None): runtime2._group_ok, (False, clf): runtime2._sguided_ok,
+             (True, clf): runtime2._gguided_ok}
+    for flag in flags.values():
+        monkeypatch.delitem(flag, dev, raising=False)              # (not checked yet on this device)
+
+    def route(b, clf_net=None, capturing=False):
+        r = runtime2.member_route(net, 32, b, dev, capturing, clf_net)
+        return None if r is None else (r.mode, r.k)
+
+    def want(b):
+        return ("split", 4) if b <= 64 else ("split", 2) if b <= 128 else ("grouped", 4) if b <= 256 else None
+    for clf_net in (None, clf):
+        assert [route(b, clf_net) for b in range(1, 301)] == [want(b) for b in range(1, 301)], clf_net
+    assert runtime2.route_info(net, 32, 256, dev)["mode"] == "grouped" and runtime2.route_info(net, 32, 32, dev)["mode"] == "split"
+    for (group, clf_net), flag in flags.items():
+        monkeypatch.setitem(flag, dev, False)
+        gone, kept = (200, 32) if group else (32, 200)
+        other = clf if clf_net is None else None
+        assert route(gone, clf_net) is None and route(kept, clf_net) == want(kept) and route(gone, other) == want(gone), (group, clf_net)
+        monkeypatch.delitem(flag, dev)
+    for clf_net in (None, clf):
+        assert route(32, clf_net, capturing=True) is None and route(200, clf_net, capturing=True) is None
+    monkeypatch.setitem(runtime._prof, "buf", torch.zeros(1))
+    assert [route(b, c) for b in (32, 200) for c in (None, clf)] == [None] * 4
+    monkeypatch.setenv("CDX_UNET2_GROUP_PROF", "1")              # (tools/op_profile2.py: the unguided grouped program only)
+    assert route(200) == ("grouped", 4) and route(32) is None and route(200, clf) is None
+    monkeypatch.setitem(runtime._prof, "buf", None)
+    monkeypatch.setenv("CDX_UNET2_ASSUME_WHOLE_CHIP", "0")
+    assert [route(b, c) for b in (32, 100, 200) for c in (None, clf)] == [None] * 6
+    assert runtime2.route_info(net, 32, 256, dev)["mode"] == "plain"
+
+
+def test_a_lost_granule_turns_every_member_mode_off():
+    """with both unguided modes already off, a lost granule reported by a guided split / grouped launch must still turn the
+    guided modes off, with the warning and the report -- one guard over all four flags."""
+    dev = torch.device("cuda", 0)
+    flags = (runtime2._split_ok, runtime2._group_ok, runtime2._gguided_ok, runtime2._sguided_ok)
+    state = (*flags, runtime2._split_errs, runtime2.last_exchange_error)
+    saved = [dict(d) for d in state]
+    try:
+        word = torch.zeros(8, dtype=torch.int32)
+        word[0] = word[1] = 1                                       # failed; what = a granule
+        runtime2._split_errs[dev] = (word, word.numpy())
+        runtime2._split_ok[dev] = runtime2._group_ok[dev] = False
+        runtime2._gguided_ok[dev] = runtime2._sguided_ok[dev] = True
+        runtime2.last_exchange_error.pop(dev, None)
+        with pytest.warns(UserWarning, match="never received a granule"):
+            assert runtime2.note_exchange_failure(dev) is True
+        assert all(flag[dev] is False for flag in flags)
+        assert runtime2.last_exchange_error[dev]["what"] == "granule"
+    finally:
+        for d, s in zip(state, saved):
+            d.clear()
+            d.update(s)
 
 
 def test_sharded_sample_draws_the_solver_default_number_of_steps(monkeypatch):

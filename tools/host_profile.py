@@ -21,7 +21,6 @@ def main():
     for _ in range(5):
         agent.sample(prior, **kw)
     torch.cuda.synchronize()
-    os.environ["CDX_UNET2_SPLIT_SYNC"] = "0"
     t0 = time.perf_counter()
     for _ in range(300):
         agent.sample(prior, **kw)
