@@ -332,6 +332,15 @@ def gather_windows(row0: torch.Tensor, fields, rows: int):
     return outs
 
 
+def _wgrad_operand(t: torch.Tensor) -> torch.Tensor:
+    """The weight-gradient kernels read an operand as float4 whenever its row stride and the column are multiples of 4 floats, without
+    looking at the base address: a view whose first element is not 16-byte aligned (a column block starting at an odd column, a flat
+    buffer cut at an odd offset) is copied first."""
+    if t.shape[0] > 0 and _rows(t) % 4 == 0 and t.data_ptr() % 16 != 0:
+        return t.clone(memory_format=torch.contiguous_format)
+    return t
+
+
 def conv_wgrad(p: torch.Tensor, q: torch.Tensor, batch: int, l_p: int, l_q: int, taps: int, stride: int = 1, pad: int = 0,
                k_split: int = 0, bias_grad: bool = False, dw_out: Optional[torch.Tensor] = None, db_out: Optional[torch.Tensor] = None):
     """dw[a][b][t] = sum_{n, m} p[(n, m)][a] * q[(n, m * stride + t - pad)][b] -> (ca, cb, taps), the layout of nn.Conv1d.weight with
@@ -341,6 +350,7 @@ def conv_wgrad(p: torch.Tensor, q: torch.Tensor, batch: int, l_p: int, l_q: int,
     the kernel accumulates with float atomics either way) -- nothing is allocated or zeroed."""
     ca, cb = p.shape[1], q.shape[1]
     assert p.shape[0] == batch * l_p and q.shape[0] == batch * l_q
+    p, q = _wgrad_operand(p), _wgrad_operand(q)
     n_w = ca * cb * taps
     if dw_out is not None:
         assert dw_out.is_contiguous() and dw_out.numel() == n_w and dw_out.dtype == torch.float32
@@ -368,15 +378,20 @@ def conv_wgrad_batch(jobs) -> int:
     """The weight-gradient products ``(p, q, batch, l_p, l_q, taps, stride, pad, dw_out, db_out | None)`` of many layers, ADDED into
     their ``dw_out`` / ``db_out`` tensors (parameters' ``.grad``) by ceil(n / 32) launches of ``cdx_conv_wgrad_batch_f32``.  Each
     product is cut into ~WGRAD_JOB_WGS workgroups: big layers get few, long row slices (every slice ends in one float atomic per
-    output element), small layers many.  -> launches issued."""
+    output element), small layers many.  A product over zero rows (an empty batch) adds nothing and is left out, as ``conv_wgrad``
+    leaves it out.  -> launches issued."""
+    jobs = [j for j in jobs if j[0].shape[0] > 0]
     n_launch = 0
     for lo in range(0, len(jobs), WGRAD_BATCH):
         part = jobs[lo:lo + WGRAD_BATCH]
         b = CdxWgradBatch()
         b.n_jobs = len(part)
         start = 0
+        alive = []                                        # (copies of unaligned operands, until the launch is issued)
         for j, (p, q, batch, l_p, l_q, taps, stride, pad, dw, db) in enumerate(part):
             ca, cb = p.shape[1], q.shape[1]
+            p, q = _wgrad_operand(p), _wgrad_operand(q)
+            alive += [p, q]
             assert p.shape[0] == batch * l_p and q.shape[0] == batch * l_q and dw.is_contiguous() and dw.numel() == ca * cb * taps
             tiles = -(-ca // 64) * -(-cb // 64) * taps
             chunks = -(-(batch * l_p) // 16)

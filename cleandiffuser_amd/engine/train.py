@@ -78,8 +78,10 @@ def _wants_grad(net, *tensors) -> bool:
 # backward pass (DiffusionModel._loss_backward, and the HIP graph captured from it) the nodes therefore add straight into `p.grad` and
 # report "no gradient" to autograd.  Anywhere else -- torch.autograd.grad(), a user's own backward() over loss(), parameters with
 # hooks, views of parameters -- autograd's own accumulation runs as before.
-_in_place_depth = 0          # (module-wide, not thread-local: autograd runs the nodes of a device on its own worker thread)
-_in_place_scopes: list = []  # one entry per open grads_in_place(): the ids of the parameters it covers, or None = every parameter
+# one entry per open grads_in_place(), innermost last: [the ids of the parameters it covers, or None = every parameter].  The entry
+# itself (compared by identity) is what the scope's weight-gradient queues are filed under.  (Module-wide, not thread-local: autograd
+# runs the nodes of a device on its own worker thread)
+_in_place_scopes: list = []
 
 
 @contextlib.contextmanager
@@ -87,15 +89,16 @@ def grads_in_place(params=None):
     """`params`: the parameters of the agent whose update() this is -- only THEY take gradients in place while the scope is
     open (the flag is process-wide because autograd's worker threads run the nodes; another thread's backward over another net keeps
     autograd's own accumulation).  None: every parameter (tests, a caller that owns the process)."""
-    global _in_place_depth
-    scope = None if params is None else {id(p) for p in params}
-    _in_place_depth += 1
+    scope = [None if params is None else {id(p) for p in params}]
     _in_place_scopes.append(scope)
     try:
         yield
     finally:
-        _in_place_depth -= 1
-        _in_place_scopes.remove(scope)
+        _in_place_scopes[:] = [sc for sc in _in_place_scopes if sc is not scope]
+        # a backward pass that ended has flushed its queue itself (end-of-pass callback).  One that is still here raised before its
+        # callback could run: its products belong to no step any more
+        for task in [t for t, (owner, _) in _wgrad_queues.items() if owner is scope]:
+            del _wgrad_queues[task]
 
 
 def _reducer_may_listen() -> bool:
@@ -110,9 +113,9 @@ def _reducer_may_listen() -> bool:
 
 def _grad_slot(p) -> Optional[torch.Tensor]:
     """``p.grad`` as the tensor a kernel may add p's gradient into (created zeroed if missing), or None: autograd accumulates."""
-    if _in_place_depth <= 0 or os.environ.get("CDX_TRAIN_INPLACE_GRADS", "1") == "0":
+    if not _in_place_scopes or os.environ.get("CDX_TRAIN_INPLACE_GRADS", "1") == "0":
         return None
-    if not any(sc is None or id(p) in sc for sc in _in_place_scopes) or _reducer_may_listen():
+    if not any(ids is None or id(p) in ids for (ids,) in _in_place_scopes) or _reducer_may_listen():
         return None
     if not isinstance(p, nn.Parameter) or not p.is_leaf or not p.requires_grad or p.dtype != torch.float32 or p._backward_hooks or \
             getattr(p, "_post_accumulate_grad_hooks", None):
@@ -137,34 +140,31 @@ def _written(*grads):
 # update()'s backward they are QUEUED by the nodes and issued when the backward pass ends, all layers in ceil(n / 32) launches of
 # cdx_conv_wgrad_batch_f32 -- round 5 issued 65 launches of 4-20 us each, 38 % of a config-2 step's device time at 3.8 % of the
 # matrix pipe's peak, none of them able to fill the chip.  CDX_TRAIN_WGRAD_BATCH=0: one launch per layer as before.
-_wgrad_queues: dict = {}     # autograd graph-task id -> the products queued by that backward pass
+_wgrad_queues: dict = {}     # autograd graph-task id -> (the grads_in_place() scope it was opened under, the products queued)
 
 
 def _queue_wgrad(job) -> bool:
-    if _in_place_depth <= 0 or os.environ.get("CDX_TRAIN_WGRAD_BATCH", "1") == "0":
+    if not _in_place_scopes or os.environ.get("CDX_TRAIN_WGRAD_BATCH", "1") == "0":
         return False
     task = torch._C._current_graph_task_id()
     if task < 0:
         return False                                       # not inside a backward pass (a node called by hand): launch now
-    q = _wgrad_queues.get(task)
-    if q is None:
-        # a new backward pass (a re-entrant one inside another keeps its own list).  Lists that an EARLIER pass left behind -- it raised
-        # before its end-of-pass callback ran -- belong to no step any more: drop them
-        for old in [t for t in _wgrad_queues if t < task - 4]:
-            del _wgrad_queues[old]
-        q = []
-
+    entry = _wgrad_queues.get(task)
+    if entry is None:
+        # a new backward pass.  A re-entrant one inside another keeps its own list, and the outer pass's list stays where it is however
+        # many passes run inside it (graph-task ids say nothing about which pass is still alive).  A list whose pass raised before its
+        # end-of-pass callback ran is dropped when the scope it was opened under closes (grads_in_place)
         def flush(task=task):
-            jobs = _wgrad_queues.pop(task, None)
-            if jobs:
-                blocks.conv_wgrad_batch(jobs)
+            left = _wgrad_queues.pop(task, None)
+            if left and left[1]:
+                blocks.conv_wgrad_batch(left[1])
         try:
             # (runs when this backward pass ends, on the stream it was called on -- what DDP's reducer relies on too)
             torch.autograd.Variable._execution_engine.queue_callback(flush)
         except RuntimeError:
             return False
-        _wgrad_queues[task] = q
-    q.append(job)
+        entry = _wgrad_queues[task] = (_in_place_scopes[-1], [])
+    entry[1].append(job)
     return True
 
 

@@ -10,6 +10,7 @@ import torch
 
 from oracle import cases
 from conftest import golden_path
+from gpu_profile import profiled as _profiled
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -46,22 +47,6 @@ def _native_loaded():
     for nb in (8, 200):
         gagent.sample(torch.zeros(nb, 32, 23, device=DEV), n_samples=nb, solver="ddpm", sample_steps=2, w_cg=0.1)
     torch.cuda.synchronize()
-
-
-def _profiled(body, activities=None, rerun=True):
-    """torch.profiler over ``body()`` -> (profiler, body's result).  roctracer occasionally hands the profiler NO device activity for a
-    region (one full-suite run in ~25 this round: every kernel name missing, only the host-side ops listed).  A test that asserts on
-    kernel names then has nothing to look at: the region is profiled once more where running it again is harmless (`rerun`), else the
-    test is skipped rather than failed for a tracing dropout."""
-    from torch.profiler import profile, ProfilerActivity
-    acts = activities or [ProfilerActivity.CPU, ProfilerActivity.CUDA]
-    for attempt in range(2 if rerun else 1):
-        with profile(activities=acts) as prof:
-            out = body()
-            torch.cuda.synchronize()
-        if any(e.device_time_total > 0 for e in prof.key_averages()):
-            return prof, out
-    pytest.skip("torch.profiler recorded no device activity for this region (roctracer dropout)")
 
 
 def _spy_launches(monkeypatch):
@@ -1542,6 +1527,37 @@ def test_layernorm_and_attention_backward_kernels_match_autograd():
         torch.testing.assert_close(got, qkv.grad, rtol=2e-4, atol=2e-5)
 
 
+@pytest.mark.parametrize("M,C,T,blocks_of", [(66, 1500, 33, None), (66, 1500, 33, 1536), (40, 320, 10, 400), (24, 2050, 8, 2100), (35, 1023, 7, None)])
+def test_layernorm_backward_against_float64_on_column_blocks(M, C, T, blocks_of):
+    """cdx_layernorm_bwd_f32 against float64 autograd ON THE CPU: the <32> variant (1024 < C <= 2048), odd widths, and dy / x as column
+    blocks of wider matrices (lddy != C, ldx != C, first column 3: no alignment to lean on)."""
+    import torch.nn.functional as F
+    from cleandiffuser_amd.engine import blocks
+    g = torch.Generator().manual_seed(M + C)
+    x, dy = torch.randn(M, C, generator=g) * 2 + 0.5, torch.randn(M, C, generator=g)
+    gamma, beta = torch.randn(C, generator=g), torch.randn(C, generator=g)
+    mod = torch.randn(M // T, 2 * C, generator=g)
+    if blocks_of:
+        xd, dyd = (torch.randn(M, blocks_of, generator=g).to(DEV)[:, 3:3 + C].copy_(t) for t in (x, dy))
+        assert xd.stride(0) == blocks_of
+    else:
+        xd, dyd = x.to(DEV), dy.to(DEV)
+    x64, g64, m64 = (t.double().requires_grad_(True) for t in (x, gamma, mod))
+    F.layer_norm(x64, (C,), g64, beta.double(), 1e-5).backward(dy.double())
+    dx, dyx = blocks.layernorm_backward(dyd, xd, gamma=gamma.to(DEV), eps=1e-5, want_dyxhat=True)
+    torch.testing.assert_close(dx.cpu().double(), x64.grad, rtol=2e-4, atol=2e-5)
+    torch.testing.assert_close(dyx.cpu().double().sum(0), g64.grad, rtol=2e-4, atol=2e-4)
+    x64.grad = None
+    (F.layer_norm(x64, (C,), eps=1e-6).view(M // T, T, C) * (1 + m64[:, None, :C]) + m64[:, None, C:]).view(M, C).backward(dy.double())
+    scale = mod.to(DEV)[:, :C]                               # (a column block itself: ldmod = 2 C)
+    dx, dyx = blocks.layernorm_backward(dyd, xd, scale=scale, rows_per_mod=T, eps=1e-6, want_dyxhat=True)
+    torch.testing.assert_close(dx.cpu().double(), x64.grad, rtol=2e-4, atol=2e-5)
+    torch.testing.assert_close(dyx.cpu().double().view(M // T, T, C).sum(1), m64.grad[:, :C], rtol=2e-4, atol=2e-4)
+    x64.grad = None
+    F.layer_norm(x64, (C,), eps=1e-5).backward(dy.double())
+    torch.testing.assert_close(blocks.layernorm_backward(dyd, xd, eps=1e-5).cpu().double(), x64.grad, rtol=2e-4, atol=2e-5)
+
+
 def _mha_reference(q, k, v, B, H, mask, keep):
     """softmax(q k^T / sqrt(dh) + mask) o keep @ v in plain torch ops (what F.multi_head_attention_forward computes between the
     projections in train mode, with the dropout mask given instead of drawn)."""
@@ -1795,6 +1811,29 @@ def test_groupnorm_backward_in_registers_and_its_position_sums(B, L, C, G, act):
             sc = float(gr.grad.abs().max()) + float(br.grad.abs().max())
             torch.testing.assert_close(dg.cpu(), gr.grad, rtol=2e-4, atol=5e-5 * sc + 1e-6)
             torch.testing.assert_close(db.cpu(), br.grad, rtol=2e-4, atol=5e-5 * sc + 1e-6)
+
+
+@pytest.mark.parametrize("B,L,C,G", [(5, 8, 48, 4), (3, 200, 24, 2)])
+@pytest.mark.parametrize("act", ["mish", "none"])
+def test_groupnorm_backward_of_a_group_width_that_is_no_power_of_two(B, L, C, G, act):
+    """Groups of 12 channels (96 and 2400 elements per group): dx out of the scalar kernel against float64 autograd on the CPU; the
+    parameter gradients and position sums need a power-of-two width and are refused with CDX_EINVAL, nothing written."""
+    import torch.nn.functional as F
+    from cleandiffuser_amd.engine import blocks
+    g = torch.Generator().manual_seed(B + L + C)
+    x, dy = torch.randn(B * L, C, generator=g), torch.randn(B * L, C, generator=g)
+    gamma, beta = torch.randn(C, generator=g), torch.randn(C, generator=g)
+    xr, gr, br = (t.double().requires_grad_(True) for t in (x, gamma, beta))
+    y = F.group_norm(xr.view(B, L, C).permute(0, 2, 1), G, gr, br, 1e-5)
+    (F.mish(y) if act == "mish" else y).permute(0, 2, 1).reshape(B * L, C).backward(dy.double())
+    args = (dy.to(DEV), x.to(DEV), gamma.to(DEV), beta.to(DEV), B, L, G)
+    dx = blocks.groupnorm_backward(*args, act=act)
+    torch.testing.assert_close(dx.cpu().double(), xr.grad, rtol=2e-4, atol=2e-5)
+    acc = (torch.zeros(C, device=DEV), torch.zeros(C, device=DEV))
+    for kw in (dict(param_grads=True), dict(param_grads=True, grads_out=acc), dict(possum_out=torch.zeros(B, C, device=DEV))):
+        with pytest.raises(RuntimeError, match="failed with code -1"):
+            blocks.groupnorm_backward(*args, act=act, **kw)
+    assert float(acc[0].abs().max()) == 0.0 and float(acc[1].abs().max()) == 0.0
 
 
 def test_relayout_kernel_builds_every_weight_layout_and_the_registry_keeps_them_current(amd_lib, monkeypatch):
@@ -2058,13 +2097,92 @@ def test_batched_weight_gradients_equal_the_single_launches(n_jobs):
             ok = (idx >= 0) & (idx < l_q)
             ref[:, :, t] = torch.einsum("nma,nmb->ab", p3[:, ok], q3[:, idx[ok]])
         refs.append((seed_w.double().cpu() + ref, seed_b.double().cpu() + p.double().cpu().sum(0)))
-    assert blocks.conv_wgrad_batch(jobs) == -(-n_jobs // 32)
+    # (a product over zero rows -- an empty batch -- rides along: left out like conv_wgrad leaves it out, no launch, nothing added)
+    keep_w, keep_b = torch.randn(8, 8, 3, generator=g).to(DEV), torch.randn(8, generator=g).to(DEV)
+    empty = (torch.zeros(0, 8, device=DEV), torch.zeros(0, 8, device=DEV), 0, 16, 16, 3, 1, 1, keep_w.clone(), keep_b.clone())
+    assert blocks.conv_wgrad_batch([empty] + jobs) == -(-n_jobs // 32) and blocks.conv_wgrad_batch([empty]) == 0
     torch.cuda.synchronize()
+    assert torch.equal(empty[8], keep_w) and torch.equal(empty[9], keep_b)
     for (p, q, batch, l_p, l_q, taps, stride, pad, dw, db), (rw, rb), (sw, sb) in zip(jobs, refs, singles):
         scale = max(1.0, float(rw.abs().max()))
         assert float((dw.double().cpu() - rw).abs().max()) <= 2e-5 * scale
         if db is not None:
             assert float((db.double().cpu() - rb).abs().max()) <= 2e-5 * max(1.0, float(rb.abs().max()))
+
+
+def _wgrad_ref(p, q, batch, l_p, l_q, taps, stride, pad):
+    p3, q3 = p.double().view(batch, l_p, -1), q.double().view(batch, l_q, -1)
+    ref = torch.zeros(p3.shape[2], q3.shape[2], taps, dtype=torch.float64)
+    m = torch.arange(l_p)
+    for t in range(taps):
+        idx = m * stride + t - pad
+        ok = (idx >= 0) & (idx < l_q)
+        ref[:, :, t] = torch.einsum("nma,nmb->ab", p3[:, ok], q3[:, idx[ok]])
+    return ref
+
+
+# (batch, l_p, l_q, taps, stride, pad, ca, cb): 256 x 32 = 512 whole 16-row chunks; 255 x 31 = 7905 rows = 494 chunks + 1 row
+WGRAD_MANY_SLICES = [(256, 32, 32, 1, 1, 0, 64, 64), (255, 31, 31, 1, 1, 0, 23, 130), (255, 31, 31, 5, 1, 2, 65, 23), (256, 32, 32, 5, 1, 2, 130, 65),
+                     (255, 31, 31, 16, 1, 8, 23, 64), (256, 16, 31, 3, 2, 1, 64, 130), (255, 31, 63, 3, 2, 1, 130, 23), (256, 32, 64, 4, 2, 1, 65, 64)]
+
+
+@pytest.mark.parametrize("bias", [False, True])
+@pytest.mark.parametrize("batch,l_p,l_q,taps,stride,pad,ca,cb", WGRAD_MANY_SLICES)
+def test_weight_gradients_over_many_row_slices_against_float64(batch, l_p, l_q, taps, stride, pad, ca, cb, bias):
+    """The accumulation every real update() uses -- thousands of rows cut into up to 64 slices, each ending in float atomics onto the
+    gradient -- against the float64 einsum: slice counts chosen by the library (0), one slice, 7 slices of unequal length, and 64
+    (of 7905 rows = 495 chunks: 8 chunks per slice, the last two slices EMPTY and the one before ends in a one-row chunk); the same
+    products through the batched launch; 1 / 3 / 4 / 5 / 16 taps, stride 2 over an odd length, widths 23 / 64 / 65 / 130; ADDED onto
+    what the gradient holds; twice (float atomics: the two runs agree within the bar, not bit for bit)."""
+    from cleandiffuser_amd.engine import blocks
+    g = torch.Generator().manual_seed(batch + taps * 7 + ca)
+    p, q = torch.randn(batch * l_p, ca, generator=g), torch.randn(batch * l_q, cb, generator=g)
+    seed_w, seed_b = torch.randn(ca, cb, taps, generator=g), torch.randn(ca, generator=g)
+    rw = seed_w.double() + _wgrad_ref(p, q, batch, l_p, l_q, taps, stride, pad)
+    rb = seed_b.double() + p.double().sum(0)
+    bar_w, bar_b = 2e-5 * max(1.0, float(rw.abs().max())), 2e-5 * max(1.0, float(rb.abs().max()))
+    pd, qd = p.to(DEV), q.to(DEV)
+
+    def run(k_split):
+        dw, db = seed_w.clone().to(DEV), (seed_b.clone().to(DEV) if bias else None)
+        if k_split == "batch":
+            assert blocks.conv_wgrad_batch([(pd, qd, batch, l_p, l_q, taps, stride, pad, dw, db)]) == 1
+        else:
+            blocks.conv_wgrad(pd, qd, batch, l_p, l_q, taps, stride, pad, k_split=k_split, bias_grad=bias, dw_out=dw, db_out=db)
+        return dw.cpu().double(), (db.cpu().double() if bias else None)
+    for k_split in (0, 1, 7, 64, "batch"):
+        (w1, b1), (w2, b2) = run(k_split), run(k_split)
+        for w in (w1, w2):
+            assert float((w - rw).abs().max()) <= bar_w, (k_split, float((w - rw).abs().max()), bar_w)
+        assert float((w1 - w2).abs().max()) <= bar_w, k_split
+        if bias:
+            for b in (b1, b2):
+                assert float((b - rb).abs().max()) <= bar_b, (k_split, float((b - rb).abs().max()), bar_b)
+            assert float((b1 - b2).abs().max()) <= bar_b, k_split
+
+
+def test_weight_gradients_of_operands_whose_first_element_is_not_16_byte_aligned():
+    """wg_load4 takes its float4 load from the row stride and the column alone.  blocks.conv_wgrad / conv_wgrad_batch accept any strided
+    view, so they copy an operand with a 4-float row stride whose base is not 16-byte aligned: a column block starting at an odd
+    column, a contiguous matrix cut out of a flat buffer at an odd offset (``.contiguous()`` returns such a view unchanged)."""
+    from cleandiffuser_amd.engine import blocks
+    g = torch.Generator().manual_seed(9)
+    batch, l, ca, cb = 6, 16, 64, 32
+    p = torch.randn(batch * l, ca + 8, generator=g).to(DEV)[:, 1:1 + ca]
+    q = torch.randn(1 + batch * l * cb, generator=g).to(DEV)[1:].view(batch * l, cb)
+    assert p.stride(0) % 4 == 0 and p.data_ptr() % 16 != 0 and q.is_contiguous() and q.data_ptr() % 16 != 0
+    assert all(blocks._wgrad_operand(t).data_ptr() % 16 == 0 and torch.equal(blocks._wgrad_operand(t), t) for t in (p, q))
+    ref = _wgrad_ref(p.cpu(), q.cpu(), batch, l, l, 3, 1, 1)
+    rb = p.double().cpu().sum(0)
+    dw, db = blocks.conv_wgrad(p, q, batch, l, l, 3, 1, 1, bias_grad=True)
+    jobs = [(p, q, batch, l, l, 3, 1, 1, torch.zeros(ca, cb, 3, device=DEV), torch.zeros(ca, device=DEV)),
+            (q, p, batch, l, l, 3, 1, 1, torch.zeros(cb, ca, 3, device=DEV), None)]
+    assert blocks.conv_wgrad_batch(jobs) == 1
+    bar = 2e-5 * max(1.0, float(ref.abs().max()))
+    assert float((dw.double().cpu() - ref).abs().max()) <= bar and float((jobs[0][8].double().cpu() - ref).abs().max()) <= bar
+    assert float((db.double().cpu() - rb).abs().max()) <= bar and float((jobs[0][9].double().cpu() - rb).abs().max()) <= bar
+    ref_t = _wgrad_ref(q.cpu(), p.cpu(), batch, l, l, 3, 1, 1)
+    assert float((jobs[1][8].double().cpu() - ref_t).abs().max()) <= 2e-5 * max(1.0, float(ref_t.abs().max()))
 
 
 def test_a_failed_capture_falls_back_to_the_eager_step_and_keeps_earlier_gradients(amd_lib, monkeypatch):

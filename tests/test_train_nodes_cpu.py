@@ -240,3 +240,95 @@ def test_a_copied_module_starts_with_an_empty_layout_registry():
         y0, y1 = fwd(net, args[0], *args[1:]), fwd(twin, args[0], *args[1:])       # and the twin builds its own
         assert torch.equal(y0, y1) and twin._cdx_weight_packs.entries
         assert all(k not in net._cdx_weight_packs.entries for k in twin._cdx_weight_packs.entries)
+
+
+def _chain(x, y_up):
+    """net_down's input: the sample, moved by net_up's output (broadcast where that net maps a sequence to one number per sample)."""
+    return x + 0.1 * y_up.reshape(y_up.shape + (1,) * (x.dim() - y_up.dim()))
+
+
+def _nested_graph(nets, fwds, args, wgts, n_nested):
+    """net_up -> a node whose backward() runs `n_nested` complete forward + backward passes of net_mid -> net_down, then .backward()."""
+    up, mid, down = nets
+
+    class Nested(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, h):
+            return h.clone()
+
+        @staticmethod
+        def backward(ctx, g):
+            with torch.enable_grad():
+                for _ in range(n_nested):
+                    (fwds[1](mid, args[0].clone().requires_grad_(True), *args[1:]) * wgts[1]).sum().backward()
+            return g
+
+    y_up = fwds[0](up, args[0].clone().requires_grad_(True), *args[1:])
+    y = fwds[2](down, Nested.apply(_chain(args[0], y_up)), *args[1:])
+    (y * wgts[2]).sum().backward()
+
+
+@pytest.mark.parametrize("batched", ["1", "0"])
+@pytest.mark.parametrize("n_nested", [0, 1, 5])
+@pytest.mark.parametrize("name", ["janner", "janner_cond", "half_janner"])
+def test_a_reentrant_backward_keeps_every_queued_weight_gradient(name, n_nested, batched, monkeypatch):
+    """a backward pass that runs inside another one's node (a re-entrant pass: gradient penalties, a guidance term computed
+    in backward()) opens weight-gradient queues of its own.  The outer pass's queue -- filled half by net_down before the nested passes,
+    half by net_up after them -- must survive them and be flushed once, whatever ids autograd gives the passes."""
+    monkeypatch.setenv("CDX_TRAIN_WGRAD_BATCH", batched)
+    nets = [_case(name)[0].train() for _ in range(3)]
+    for i, net in enumerate(nets):                          # (three different nets: same architecture, different weights)
+        load_synth(net, 20 + i)
+    _, fwd, args = _case(name)
+    wgts = [_wgt(net, args, 30 + i) for i, net in enumerate(nets)]
+    torch_fwd = lambda net, *a: net._forward_torch(*a) if hasattr(net, "_forward_torch") else net(*a)      # noqa: E731
+    for net in nets:
+        net.zero_grad(set_to_none=True)
+    _nested_graph(nets, [torch_fwd] * 3, args, wgts, n_nested)
+    want = [_grads(net) for net in nets]
+    assert any(g is not None for g in want[0].values()) and any(g is not None for g in want[2].values())
+    for net in nets:
+        net.zero_grad(set_to_none=True)
+    with emulated():
+        with train.grads_in_place():
+            _nested_graph(nets, [fwd] * 3, args, wgts, n_nested)
+        assert not train._wgrad_queues
+    for which, net, ref in zip(("net_up", "net_mid", "net_down"), nets, want):
+        for n, g in _grads(net).items():
+            _close(g, ref[n], f"{name}, {n_nested} nested passes: {which}.{n}")
+
+
+def test_a_backward_pass_that_raises_leaves_no_weight_gradient_queue_behind():
+    """The end-of-pass callback of a pass that raised never runs: what it had queued is dropped when its grads_in_place() scope closes,
+    nothing of it reaches the next step's gradients."""
+    net, fwd, args = _case("janner")
+    net.train()
+    wgt = _wgt(net, args, 1)
+    _, _, want = _reference(net, args, wgt)
+
+    class Boom(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, h):
+            return h.clone()
+
+        @staticmethod
+        def backward(ctx, g):
+            raise RuntimeError("boom")
+
+    with emulated() as counts:
+        net.zero_grad(set_to_none=True)
+        before = counts.get("wgrad_batch", 0)
+        with pytest.raises(RuntimeError, match="boom"):
+            with train.grads_in_place():
+                y = fwd(net, Boom.apply(fwd(net, args[0], *args[1:])), *args[1:])      # the second application queues, then Boom raises
+                try:
+                    (y * wgt).sum().backward()
+                finally:
+                    assert train._wgrad_queues             # (the failed pass had queued products: the case is not vacuous)
+        assert not train._wgrad_queues and counts.get("wgrad_batch", 0) == before
+        net.zero_grad(set_to_none=True)
+        with train.grads_in_place():
+            (fwd(net, args[0], *args[1:]) * wgt).sum().backward()
+        assert not train._wgrad_queues
+    for n, g in _grads(net).items():
+        _close(g, want[n], f"the step after a failed pass: {n}")
