@@ -238,6 +238,13 @@ int check_request(const cdx_sampling* s, const char* who, int max_kind) {
 
 int chunk_of(const cdx_sampling* s) { return (s->chunk > 0 && s->chunk < s->batch) ? s->chunk : s->batch; }
 
+int launch_step(hipStream_t stream, const StepArgs& a) {      // grid-stride over nb * hd elements, at most 4096 workgroups
+    const size_t n = (size_t)a.nb * a.hd;
+    const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    hipLaunchKernelGGL(solver_step_kernel, dim3(blocks), dim3(256), 0, stream, a);
+    return hip_ok();
+}
+
 int run_step(hipStream_t stream, const cdx_sampling* s, const cdx_step& st, float* x, const float* pred, float* prev,
              float* xold, int nb, int b0) {
     StepArgs a;
@@ -247,10 +254,7 @@ int run_step(hipStream_t stream, const cdx_sampling* s, const cdx_step& st, floa
     a.st = st; a.nb = nb; a.hd = s->hd; a.b0 = b0; a.batch = s->batch;
     a.predict_noise = s->predict_noise; a.cfg_mode = s->cfg_mode; a.cfg_w = s->cfg_w;
     a.grad = nullptr; a.cg_scale = 0.f;
-    const size_t n = (size_t)nb * s->hd;
-    const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    hipLaunchKernelGGL(solver_step_kernel, dim3(blocks), dim3(256), 0, stream, a);
-    return hip_ok();
+    return launch_step(stream, a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -341,7 +345,7 @@ int dit_prepare(const cdx_dit1d_weights* w, const cdx_sampling* s, hipStream_t s
 }
 
 int dit_forward(const cdx_dit1d_weights* w, const cdx_sampling* s, hipStream_t st, const DitBuffers& B, const float* x,
-                float* pred, int nb, int rec, float in_scale = 1.0f) {
+                float* pred, int nb, int /* b0 */, int rec, float in_scale) {
     const int two = s->cfg_mode == 2 ? 2 : 1, bf = nb * two;
     const int T = w->tokens, d = w->d_model, rows = bf * T;
     const int xw = w->in_dim * (w->cross ? 2 : 1);                                 // width of a state row
@@ -492,7 +496,7 @@ int ptf_prepare(const cdx_pearcetf_weights* w, const cdx_sampling* s, hipStream_
 }
 
 int ptf_forward(const cdx_pearcetf_weights* w, const cdx_sampling* s, hipStream_t st, const PtfBuffers& B, const float* x, float* pred,
-                int nb, int rec, float in_scale = 1.0f) {
+                int nb, int /* b0 */, int rec, float in_scale) {
     const int two = s->cfg_mode == 2 ? 2 : 1, bf = nb * two;
     const int S = 2 + w->To, te = w->te, td = w->te * w->n_heads, E = w->emb_dim, rows = bf * S;
     CDX_TRY(scaled_input(st, x, pred, in_scale, (size_t)nb * w->act_dim));
@@ -727,7 +731,7 @@ int tf_prepare(const cdx_chitf_weights* w, const cdx_sampling* s, hipStream_t st
 }
 
 int tf_forward(const cdx_chitf_weights* w, const cdx_sampling* s, hipStream_t st, const TfBuffers& B, const float* x, float* pred,
-               int nb, int rec, float in_scale = 1.0f) {
+               int nb, int /* b0 */, int rec, float in_scale) {
     const int two = s->cfg_mode == 2 ? 2 : 1, bf = nb * two;
     const int T = w->Ta, d = w->d_model, rows = bf * T, orow = bf * w->To;
     CDX_TRY(scaled_input(st, x, pred, in_scale, (size_t)nb * T * w->act_dim));    // pred is free until the head writes it
@@ -1342,6 +1346,39 @@ struct HjPass {
     }
 };
 
+// The chunk loop of the executors with a fixed buffer layout (DiT1d, PearceTransformer, ChiTransformer, residual MLP; the U-Net sizes
+// and runs in one walk, chiunet_pass): check, lay the workspace out, then per chunk of the batch prepare what all records share and
+// run either one forward (n_steps == 0) or the loop on a workspace copy of the state.  EDM-family records (kind >= 5) evaluate the
+// network on c_in * x: their alpha is the input scale.
+template <class Buf, class W, class Check, class Layout, class Prepare, class Forward>
+int run_chunks(const W* w, const cdx_sampling* s, void* hip_stream, const char* too_small, Check check, Layout layout, Prepare prepare,
+               Forward forward) {
+    CDX_TRY(check(w, s));
+    if (s->batch == 0) return CDX_OK;
+    Buf B;
+    const long long need = layout(w, s, s->workspace, &B);
+    if (!s->workspace || s->workspace_floats < need) { cdx_set_err(too_small); return CDX_EINVAL; }
+    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+    const int chunk = chunk_of(s);
+    for (int b0 = 0; b0 < s->batch; b0 += chunk) {
+        const int nb = s->batch - b0 < chunk ? s->batch - b0 : chunk;
+        const size_t off = (size_t)b0 * s->hd, bytes = (size_t)nb * s->hd * sizeof(float);
+        CDX_TRY(prepare(w, s, st, B, nb, b0));
+        if (s->n_steps == 0) {
+            CDX_TRY(forward(w, s, st, B, s->x_in + off, s->x_out + off, nb, b0, 0, 1.0f));
+            continue;
+        }
+        if (hipMemcpyAsync(B.x, s->x_in + off, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return hip_ok();
+        for (int i = 0; i < s->n_steps; ++i) {
+            const cdx_step& rec = s->steps[i];
+            CDX_TRY(forward(w, s, st, B, B.x, B.pred, nb, b0, i, rec.kind >= 5 ? rec.alpha : 1.0f));
+            CDX_TRY(run_step(st, s, rec, B.x, B.pred, B.prev, B.xold, nb, b0));
+        }
+        if (hipMemcpyAsync(s->x_out + off, B.x, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return hip_ok();
+    }
+    return CDX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1352,29 +1389,8 @@ long long cdx_dit1d_workspace_floats(const cdx_dit1d_weights* w, const cdx_sampl
 }
 
 int cdx_dit1d_run(const cdx_dit1d_weights* w, const cdx_sampling* s, void* hip_stream) {
-    CDX_TRY(dit_check(w, s));
-    if (s->batch == 0) return CDX_OK;
-    DitBuffers B;
-    const long long need = dit_layout(w, s, s->workspace, &B);
-    if (!s->workspace || s->workspace_floats < need) { cdx_set_err("cdx_dit1d_run: workspace too small"); return CDX_EINVAL; }
-    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    const int chunk = chunk_of(s);
-    for (int b0 = 0; b0 < s->batch; b0 += chunk) {
-        const int nb = s->batch - b0 < chunk ? s->batch - b0 : chunk;
-        const size_t off = (size_t)b0 * s->hd, bytes = (size_t)nb * s->hd * sizeof(float);
-        CDX_TRY(dit_prepare(w, s, st, B, nb, b0));
-        if (s->n_steps == 0) {
-            CDX_TRY(dit_forward(w, s, st, B, s->x_in + off, s->x_out + off, nb, 0));
-            continue;
-        }
-        if (hipMemcpyAsync(B.x, s->x_in + off, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return hip_ok();
-        for (int i = 0; i < s->n_steps; ++i) {
-            CDX_TRY(dit_forward(w, s, st, B, B.x, B.pred, nb, i, s->steps[i].kind >= 5 ? s->steps[i].alpha : 1.0f));
-            CDX_TRY(run_step(st, s, s->steps[i], B.x, B.pred, B.prev, B.xold, nb, b0));
-        }
-        if (hipMemcpyAsync(s->x_out + off, B.x, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return hip_ok();
-    }
-    return CDX_OK;
+    return run_chunks<DitBuffers>(w, s, hip_stream, "cdx_dit1d_run: workspace too small", dit_check, dit_layout, dit_prepare,
+                                  dit_forward);
 }
 
 long long cdx_pearcetf_workspace_floats(const cdx_pearcetf_weights* w, const cdx_sampling* s) {
@@ -1383,29 +1399,8 @@ long long cdx_pearcetf_workspace_floats(const cdx_pearcetf_weights* w, const cdx
 }
 
 int cdx_pearcetf_run(const cdx_pearcetf_weights* w, const cdx_sampling* s, void* hip_stream) {
-    CDX_TRY(ptf_check(w, s));
-    if (s->batch == 0) return CDX_OK;
-    PtfBuffers B;
-    const long long need = ptf_layout(w, s, s->workspace, &B);
-    if (!s->workspace || s->workspace_floats < need) { cdx_set_err("cdx_pearcetf_run: workspace too small"); return CDX_EINVAL; }
-    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    const int chunk = chunk_of(s);
-    for (int b0 = 0; b0 < s->batch; b0 += chunk) {
-        const int nb = s->batch - b0 < chunk ? s->batch - b0 : chunk;
-        const size_t off = (size_t)b0 * s->hd, bytes = (size_t)nb * s->hd * sizeof(float);
-        CDX_TRY(ptf_prepare(w, s, st, B, nb, b0));
-        if (s->n_steps == 0) {
-            CDX_TRY(ptf_forward(w, s, st, B, s->x_in + off, s->x_out + off, nb, 0));
-            continue;
-        }
-        if (hipMemcpyAsync(B.x, s->x_in + off, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return hip_ok();
-        for (int i = 0; i < s->n_steps; ++i) {
-            CDX_TRY(ptf_forward(w, s, st, B, B.x, B.pred, nb, i, s->steps[i].kind >= 5 ? s->steps[i].alpha : 1.0f));
-            CDX_TRY(run_step(st, s, s->steps[i], B.x, B.pred, B.prev, B.xold, nb, b0));
-        }
-        if (hipMemcpyAsync(s->x_out + off, B.x, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return hip_ok();
-    }
-    return CDX_OK;
+    return run_chunks<PtfBuffers>(w, s, hip_stream, "cdx_pearcetf_run: workspace too small", ptf_check, ptf_layout, ptf_prepare,
+                                  ptf_forward);
 }
 
 long long cdx_chitf_workspace_floats(const cdx_chitf_weights* w, const cdx_sampling* s) {
@@ -1414,29 +1409,8 @@ long long cdx_chitf_workspace_floats(const cdx_chitf_weights* w, const cdx_sampl
 }
 
 int cdx_chitf_run(const cdx_chitf_weights* w, const cdx_sampling* s, void* hip_stream) {
-    CDX_TRY(tf_check(w, s));
-    if (s->batch == 0) return CDX_OK;
-    TfBuffers B;
-    const long long need = tf_layout(w, s, s->workspace, &B);
-    if (!s->workspace || s->workspace_floats < need) { cdx_set_err("cdx_chitf_run: workspace too small"); return CDX_EINVAL; }
-    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    const int chunk = chunk_of(s);
-    for (int b0 = 0; b0 < s->batch; b0 += chunk) {
-        const int nb = s->batch - b0 < chunk ? s->batch - b0 : chunk;
-        const size_t off = (size_t)b0 * s->hd, bytes = (size_t)nb * s->hd * sizeof(float);
-        CDX_TRY(tf_prepare(w, s, st, B, nb, b0));
-        if (s->n_steps == 0) {
-            CDX_TRY(tf_forward(w, s, st, B, s->x_in + off, s->x_out + off, nb, 0));
-            continue;
-        }
-        if (hipMemcpyAsync(B.x, s->x_in + off, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return hip_ok();
-        for (int i = 0; i < s->n_steps; ++i) {
-            CDX_TRY(tf_forward(w, s, st, B, B.x, B.pred, nb, i, s->steps[i].kind >= 5 ? s->steps[i].alpha : 1.0f));
-            CDX_TRY(run_step(st, s, s->steps[i], B.x, B.pred, B.prev, B.xold, nb, b0));
-        }
-        if (hipMemcpyAsync(s->x_out + off, B.x, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return hip_ok();
-    }
-    return CDX_OK;
+    return run_chunks<TfBuffers>(w, s, hip_stream, "cdx_chitf_run: workspace too small", tf_check, tf_layout, tf_prepare,
+                                 tf_forward);
 }
 
 int cdx_linattn_f32(const float* qkv, float* out, int32_t B, int32_t L, int32_t heads, int32_t dim_head, float scale, void* hip_stream) {
@@ -1616,9 +1590,7 @@ int cdx_guided_run(const cdx_guided_launch* g, void* hip_stream) {
         sa.noise = g->noise; sa.x_min = g->x_min; sa.x_max = g->x_max; sa.st = g->steps[i]; sa.nb = g->batch; sa.hd = g->hd;
         sa.b0 = 0; sa.batch = g->batch; sa.predict_noise = g->predict_noise; sa.cfg_mode = 0; sa.cfg_w = 0.f;
         sa.grad = grad; sa.cg_scale = g->cg_scale[i];
-        const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-        hipLaunchKernelGGL(solver_step_kernel, dim3(blocks), dim3(256), 0, st, sa);
-        CDX_TRY_SIDE(hip_ok());
+        CDX_TRY_SIDE(launch_step(st, sa));
     }
 #undef CDX_TRY_SIDE
     if (hipMemcpyAsync(g->x_out, x, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return hip_ok();
@@ -1631,29 +1603,8 @@ long long cdx_resmlp_workspace_floats(const cdx_resmlp_weights* w, const cdx_sam
 }
 
 int cdx_resmlp_run(const cdx_resmlp_weights* w, const cdx_sampling* s, void* hip_stream) {
-    CDX_TRY(mlp_check(w, s));
-    if (s->batch == 0) return CDX_OK;
-    MlpBuffers B;
-    const long long need = mlp_layout(w, s, s->workspace, &B);
-    if (!s->workspace || s->workspace_floats < need) { cdx_set_err("cdx_resmlp_run: workspace too small"); return CDX_EINVAL; }
-    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    const int chunk = chunk_of(s);
-    for (int b0 = 0; b0 < s->batch; b0 += chunk) {
-        const int nb = s->batch - b0 < chunk ? s->batch - b0 : chunk;
-        const size_t off = (size_t)b0 * s->hd, bytes = (size_t)nb * s->hd * sizeof(float);
-        if (s->n_steps == 0) {
-            CDX_TRY(mlp_forward(w, s, st, B, s->x_in + off, s->x_out + off, nb, b0, 0, 1.0f));
-            continue;
-        }
-        if (hipMemcpyAsync(B.x, s->x_in + off, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return hip_ok();
-        for (int i = 0; i < s->n_steps; ++i) {
-            const cdx_step& rec = s->steps[i];
-            CDX_TRY(mlp_forward(w, s, st, B, B.x, B.pred, nb, b0, i, rec.kind >= 5 ? rec.alpha : 1.0f));
-            CDX_TRY(run_step(st, s, rec, B.x, B.pred, B.prev, B.xold, nb, b0));
-        }
-        if (hipMemcpyAsync(s->x_out + off, B.x, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return hip_ok();
-    }
-    return CDX_OK;
+    const auto no_prepare = [](auto...) { return (int)CDX_OK; };        // (its time features arrive ready-made in s->temb)
+    return run_chunks<MlpBuffers>(w, s, hip_stream, "cdx_resmlp_run: workspace too small", mlp_check, mlp_layout, no_prepare, mlp_forward);
 }
 
 }  // extern "C"

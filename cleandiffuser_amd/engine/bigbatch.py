@@ -1,19 +1,24 @@
-"""Host side of the big-batch executors (``cdx_dit1d_run`` / ``cdx_resmlp_run``, include/cdx.h, csrc/cdx_bigbatch.hip).
+"""Host side of the big-batch executors (``cdx_dit1d_run`` / ``cdx_pearcetf_run`` / ``cdx_chitf_run`` / ``cdx_resmlp_run`` /
+``cdx_chiunet_run``, include/cdx.h, csrc/cdx_bigbatch.hip).
 
-DiT1d and IDQLMlp/NewIDQLMlp are served here: their layers are plain GEMMs over M = batch x tokens rows, so the loop of
-``sample()`` becomes a stream of tiled-GEMM / LayerNorm / attention / solver-step launches issued by ONE C call.  This
-module only marshals pointers: the checkpoint tensors are used in place (PyTorch layouts), the workspace is a cached
-device tensor, step records are the same ``plan.Step`` list the fused kernel consumes.
+The backbones served here have layers that are plain GEMMs over M = batch x tokens rows, so the loop of ``sample()`` becomes a stream
+of tiled-GEMM / LayerNorm / attention / solver-step launches issued by ONE C call.  This module only marshals pointers: the checkpoint
+tensors are used in place (PyTorch layouts), the workspace is a cached device tensor, step records are the same ``plan.Step`` list the
+fused kernel consumes.  What differs between the families -- which modules, how to bind them, the shapes they take, their chunk rule,
+their C entries -- is one row each of ``FAMILIES``; ``forward()`` and ``sample()`` are written once against a row.
 """
 import ctypes
+import functools
+import importlib
 import os
 import weakref
-from typing import Optional
+from types import SimpleNamespace
+from typing import Callable, NamedTuple, Optional
 
 import torch
 
 from . import runtime
-from .runtime import CdxStep, _check, _dense_hd, _f32c, _predicts_noise, _signature, _stream_ptr, load_library
+from .runtime import CdxStep, _check, _dense_hd, _f32c, _predicts_noise, _signature, _stream_ptr, host_steps, load_library
 
 _FP = ctypes.c_void_p
 _I = ctypes.c_int32
@@ -106,58 +111,17 @@ def _lib():
     global _declared
     lib = load_library()
     if not _declared:
-        lib.cdx_dit1d_workspace_floats.argtypes = [ctypes.POINTER(CdxDitWeights), ctypes.POINTER(CdxSampling)]
-        lib.cdx_dit1d_workspace_floats.restype = ctypes.c_longlong
-        lib.cdx_dit1d_run.argtypes = [ctypes.POINTER(CdxDitWeights), ctypes.POINTER(CdxSampling), ctypes.c_void_p]
-        lib.cdx_dit1d_run.restype = ctypes.c_int
-        lib.cdx_pearcetf_workspace_floats.argtypes = [ctypes.POINTER(CdxPearcetfWeights), ctypes.POINTER(CdxSampling)]
-        lib.cdx_pearcetf_workspace_floats.restype = ctypes.c_longlong
-        lib.cdx_pearcetf_run.argtypes = [ctypes.POINTER(CdxPearcetfWeights), ctypes.POINTER(CdxSampling), ctypes.c_void_p]
-        lib.cdx_pearcetf_run.restype = ctypes.c_int
-        lib.cdx_chitf_workspace_floats.argtypes = [ctypes.POINTER(CdxChitfWeights), ctypes.POINTER(CdxSampling)]
-        lib.cdx_chitf_workspace_floats.restype = ctypes.c_longlong
-        lib.cdx_chitf_run.argtypes = [ctypes.POINTER(CdxChitfWeights), ctypes.POINTER(CdxSampling), ctypes.c_void_p]
-        lib.cdx_chitf_run.restype = ctypes.c_int
-        lib.cdx_chiunet_workspace_floats.argtypes = [ctypes.POINTER(CdxChiUNetWeights), ctypes.POINTER(CdxSampling)]
-        lib.cdx_chiunet_workspace_floats.restype = ctypes.c_longlong
-        lib.cdx_chiunet_run.argtypes = [ctypes.POINTER(CdxChiUNetWeights), ctypes.POINTER(CdxSampling), ctypes.c_void_p]
-        lib.cdx_chiunet_run.restype = ctypes.c_int
-        lib.cdx_resmlp_workspace_floats.argtypes = [ctypes.POINTER(CdxResMlpWeights), ctypes.POINTER(CdxSampling)]
-        lib.cdx_resmlp_workspace_floats.restype = ctypes.c_longlong
-        lib.cdx_resmlp_run.argtypes = [ctypes.POINTER(CdxResMlpWeights), ctypes.POINTER(CdxSampling), ctypes.c_void_p]
-        lib.cdx_resmlp_run.restype = ctypes.c_int
+        for fam in FAMILIES:                            # cdx_<entry>_workspace_floats(weights, request), cdx_<entry>_run(weights, request, stream)
+            size, run = getattr(lib, f"cdx_{fam.entry}_workspace_floats"), getattr(lib, f"cdx_{fam.entry}_run")
+            size.argtypes, size.restype = [ctypes.POINTER(fam.weights), ctypes.POINTER(CdxSampling)], ctypes.c_longlong
+            run.argtypes, run.restype = [ctypes.POINTER(fam.weights), ctypes.POINTER(CdxSampling), ctypes.c_void_p], ctypes.c_int
         _declared = True
     return lib
 
 
 # ------------------------------------------------------------------------------------------------ #
-# backbone recognition + weight marshalling (cached per module, invalidated when a parameter changes)  #
+# weight marshalling (cached per module, invalidated when a parameter changes)                         #
 # ------------------------------------------------------------------------------------------------ #
-def is_dit1d(module) -> bool:
-    from ..nn_diffusion.dit import DiT1d
-    return type(module) is DiT1d
-
-
-def is_dit1ref(module) -> bool:
-    from ..nn_diffusion.dit import DiT1Ref
-    return type(module) is DiT1Ref
-
-
-def is_pearcetf(module) -> bool:
-    from ..nn_diffusion.pearcetransformer import PearceTransformer
-    return type(module) is PearceTransformer
-
-
-def is_resmlp(module) -> bool:
-    from ..nn_diffusion.mlp_backbones import IDQLMlp, NewIDQLMlp
-    return type(module) in (IDQLMlp, NewIDQLMlp)
-
-
-def is_chitf(module) -> bool:
-    from ..nn_diffusion.chitransformer import ChiTransformer
-    return type(module) is ChiTransformer
-
-
 class _Bound:
     """ctypes weight struct + the tensors it points into (kept alive here)."""
 
@@ -181,7 +145,7 @@ def _bind_dit(net, tokens: int, device) -> Optional[_Bound]:
     heads = net.blocks[0].attn.num_heads if len(net.blocks) else 1
     if tokens > 1024 or d > 1024 or d % heads or d // heads > 64:          # CDX_ATTN_MAX_T
         return None
-    cross_mods = list(net.cross_attns) if is_dit1ref(net) else []
+    cross_mods = list(getattr(net, "cross_attns", []))              # DiT1Ref only
     for a in [blk.attn for blk in net.blocks] + cross_mods:
         if a.in_proj_weight is None or a.in_proj_bias is None or a.bias_k is not None or a.add_zero_attn or \
                 not a.batch_first or a.num_heads != heads:
@@ -259,7 +223,7 @@ def fold_pearcetf(net) -> Optional[dict]:
     return {k: to32(v) for k, v in out.items()}
 
 
-def _bind_pearcetf(net, device) -> Optional[_Bound]:
+def _bind_pearcetf(net, _length, device) -> Optional[_Bound]:
     fold = fold_pearcetf(net)
     if fold is None:
         return None
@@ -278,7 +242,7 @@ def _bind_pearcetf(net, device) -> Optional[_Bound]:
     return _Bound(w, keep, None)
 
 
-def _bind_resmlp(net, device) -> Optional[_Bound]:
+def _bind_resmlp(net, _length, device) -> Optional[_Bound]:
     hidden = net.affine_in.out_features
     if hidden > 4096:                                  # cdx_layernorm_f32 keeps a row in registers: C <= 4096
         return None
@@ -300,7 +264,7 @@ def _bind_resmlp(net, device) -> Optional[_Bound]:
     return _Bound(w, keep, None)
 
 
-def _bind_chitf(net, device) -> Optional[_Bound]:
+def _bind_chitf(net, _length, device) -> Optional[_Bound]:
     import torch.nn as nn
     d = net.act_emb.out_features
     layers = list(net.decoder.layers)
@@ -354,183 +318,157 @@ def _bind_chitf(net, device) -> Optional[_Bound]:
     return _Bound(w, keep, None)
 
 
-def _bind_chiunet(net, Ta: int, device) -> Optional[_Bound]:
-    """ChiUNet1d (global conditioning) for the implicit-GEMM executor: conv weights are re-packed (c_out, k, c_in) once."""
-    import torch.nn as nn
-    from . import blocks as B
-    local = not net.obs_as_global_cond                  # local conditioning: one observation row per position (chiunet.py:78-82)
-    if (local and net.local_cond_encoder is None) or (not local and net.global_cond_encoder is None):
-        return None
-    n_levels = len(net.downs)
-    if local and n_levels < 2:
-        return None
-    if Ta & (Ta - 1) or (Ta >> (n_levels - 1)) < 1 or n_levels > 8:
-        return None
-    keep = []
-    p = lambda t: _dev_f32(t, keep, device)  # noqa: E731
+class _Ptrs:
+    """Device pointers of fp32 tensors; everything they point into is kept alive in ``keep``."""
 
-    def packed(t):                                      # derived tensors are always fresh fp32 device copies
-        t = t.to(device=device, dtype=torch.float32).contiguous()
-        keep.append(t)
+    def __init__(self, device):
+        self.keep, self.device = [], device
+
+    def __call__(self, t):                              # parameters that already are fp32 contiguous on the device are used in place
+        return _dev_f32(t, self.keep, self.device)
+
+    def packed(self, t):                                # derived tensors are always fresh fp32 device copies
+        t = t.to(device=self.device, dtype=torch.float32).contiguous()
+        self.keep.append(t)
         return t.data_ptr()
 
-    def bind_block(blk, cin_a, cin_b):
+    def array(self, vals):
+        a = (ctypes.c_void_p * max(len(vals), 1))(*vals)
+        self.keep.append(a)
+        return a
+
+
+def _bind_unet(net, length: int, device) -> Optional[_Bound]:
+    """ChiUNet1d / JannerUNet1d for the implicit-GEMM executor -- the walk both share: two residual blocks per level going down, the
+    middle blocks, two per level going up (the first on the concatenated skip), the resampling convolutions and the head.  Conv
+    weights are re-packed (c_out, k, c_in) once.  What differs between the two nets comes from _chiunet_adds / _janner_adds."""
+    import torch.nn as nn
+    from . import blocks as B
+    from ..nn_diffusion.jannerunet import JannerUNet1d
+    n_levels = len(net.downs)
+    if length & (length - 1) or (length >> (n_levels - 1)) < 1 or n_levels > 8:
+        return None
+    adds = (_janner_adds if type(net) is JannerUNet1d else _chiunet_adds)(net)
+    if adds is None:
+        return None
+    p = _Ptrs(device)
+
+    def bind_block(blk, cin_b=0):
         c1, gn1, c2, gn2 = blk.conv1[0], blk.conv1[1], blk.conv2[0], blk.conv2[1]
+        if adds.norm is not None and not (isinstance(gn1, adds.norm) and isinstance(gn2, adds.norm)):
+            return None
+        cin_a, film = c1.in_channels - cin_b, adds.film(blk)
         w1 = B.pack_conv(c1.weight)                     # (co, k, ci)
         has_res = isinstance(blk.residual_conv, nn.Conv1d)
         wr = blk.residual_conv.weight.detach()[:, :, 0] if has_res else None
         return CdxChiUNetBlock(
             cin_a=cin_a, cin_b=cin_b, cout=c1.out_channels, groups=gn1.num_groups,
-            w1a=packed(w1[:, :, :cin_a]), w1b=packed(w1[:, :, cin_a:]) if cin_b else None, b1=p(c1.bias), g1=p(gn1.weight),
-            be1=p(gn1.bias), w2=packed(B.pack_conv(c2.weight)), b2=p(c2.bias), g2=p(gn2.weight), be2=p(gn2.bias),
-            film_w=p(blk.cond_encoder[1].weight), film_b=p(blk.cond_encoder[1].bias),
-            wra=packed(wr[:, :cin_a]) if has_res else None, wrb=packed(wr[:, cin_a:]) if (has_res and cin_b) else None,
+            w1a=p.packed(w1[:, :, :cin_a]), w1b=p.packed(w1[:, :, cin_a:]) if cin_b else None, b1=p(c1.bias), g1=p(gn1.weight),
+            be1=p(gn1.bias), w2=p.packed(B.pack_conv(c2.weight)), b2=p(c2.bias), g2=p(gn2.weight), be2=p(gn2.bias),
+            film_w=p(film.weight), film_b=p(film.bias),
+            wra=p.packed(wr[:, :cin_a]) if has_res else None, wrb=p.packed(wr[:, cin_a:]) if (has_res and cin_b) else None,
             br=p(blk.residual_conv.bias) if has_res else None)
 
-    blocks = []
-    for res1, res2, _ in net.downs:
-        blocks += [bind_block(res1, res1.conv1[0].in_channels, 0), bind_block(res2, res2.conv1[0].in_channels, 0)]
-    blocks += [bind_block(m, m.conv1[0].in_channels, 0) for m in net.mids]
-    for res1, res2, _ in net.ups:
-        half = res1.conv1[0].in_channels // 2
-        blocks += [bind_block(res1, half, half), bind_block(res2, res2.conv1[0].in_channels, 0)]
-    if local:
-        enc1, enc2, enc_down = net.local_cond_encoder
-        # the two places the local features join have a residual conv in every real net (act_dim != model_dim; concat input)
-        if blocks[0].wra is None or blocks[len(blocks) - 2].wra is None:
-            return None
-        blocks += [bind_block(enc1, enc1.conv1[0].in_channels, 0), bind_block(enc2, enc2.conv1[0].in_channels, 0)]
+    blocks = []                                         # (a level is (block, block, ..., resampler): Janner has its attention in between)
+    for lvl in net.downs:
+        blocks += [bind_block(lvl[0]), bind_block(lvl[1])]
+    blocks += [bind_block(m) for m in adds.mids]
+    for lvl in net.ups:
+        blocks += [bind_block(lvl[0], lvl[0].conv1[0].in_channels // 2), bind_block(lvl[1])]
+    blocks = adds.more_blocks(blocks, bind_block)
+    if blocks is None or any(b is None for b in blocks):
+        return None
     for b in blocks:                                    # identity skips need matching widths; the FAST GEMM path wants 16 | c_in
         if b.wra is None and (b.cin_b or b.cin_a != b.cout):
             return None
     arr = (CdxChiUNetBlock * len(blocks))(*blocks)
-
-    def ptr_array(vals):
-        a = (ctypes.c_void_p * max(len(vals), 1))(*vals)
-        keep.append(a)
-        return a
-    downs = [lvl[2].conv for lvl in net.downs if not isinstance(lvl[2], nn.Identity)]
-    ups = [lvl[2].conv for lvl in net.ups if not isinstance(lvl[2], nn.Identity)]
+    downs = [lvl[-1].conv for lvl in net.downs if not isinstance(lvl[-1], nn.Identity)]
+    ups = [lvl[-1].conv for lvl in net.ups if not isinstance(lvl[-1], nn.Identity)]
     if len(downs) != n_levels - 1 or len(ups) != n_levels - 1:
         return None
     up_packed = [B.pack_conv_transpose_k4s2p1(u.weight) for u in ups]
     fin = net.final_conv
-    E = net.emb_dim
-    w = CdxChiUNetWeights()
-    w.act_dim, w.Ta, w.emb_dim = net.downs[0][0].conv1[0].in_channels, Ta, E
-    w.cond_dim = 0 if local else net.global_cond_encoder.in_features
-    w.kernel_size, w.n_levels, w.cond_predict_scale = fin[0].kernel_size[0], n_levels, int(net.downs[0][0].cond_predict_scale)
-    w.model_dim, w.final_groups = net.model_dim, fin[1].num_groups
-    w.emb_hidden, w.emb_out, w.film_ld = net.map_emb[0].out_features, E, (E if local else 2 * E)
+    w = CdxChiUNetWeights(Ta=length, n_levels=n_levels, model_dim=net.model_dim, final_groups=fin[1].num_groups,
+                          emb_hidden=net.map_emb[0].out_features, **adds.header)
     w.map0_w, w.map0_b, w.map2_w, w.map2_b = p(net.map_emb[0].weight), p(net.map_emb[0].bias), p(net.map_emb[2].weight), p(net.map_emb[2].bias)
-    if local:
-        w.gce_w, w.gce_b = None, None
-        w.local_obs_dim = net.local_cond_encoder[0].conv1[0].in_channels
-        w.lc_down_w, w.lc_down_b = packed(B.pack_conv(net.local_cond_encoder[2].conv.weight)), p(net.local_cond_encoder[2].conv.bias)
-    else:
-        w.gce_w, w.gce_b = p(net.global_cond_encoder.weight), p(net.global_cond_encoder.bias)
     w.blocks = arr
-    w.down_w, w.down_b = ptr_array([packed(B.pack_conv(d.weight)) for d in downs]), ptr_array([p(d.bias) for d in downs])
-    w.up_w_even, w.up_w_odd = ptr_array([packed(e) for e, _ in up_packed]), ptr_array([packed(o) for _, o in up_packed])
-    w.up_b = ptr_array([p(u.bias) for u in ups])
-    w.fin_w, w.fin_b, w.fin_g, w.fin_be = packed(B.pack_conv(fin[0].weight)), p(fin[0].bias), p(fin[1].weight), p(fin[1].bias)
-    w.out_w, w.out_b = packed(fin[3].weight.detach()[:, :, 0]), p(fin[3].bias)
-    keep.append(arr)
-    return _Bound(w, keep, None)
+    w.down_w, w.down_b = p.array([p.packed(B.pack_conv(d.weight)) for d in downs]), p.array([p(d.bias) for d in downs])
+    w.up_w_even, w.up_w_odd = p.array([p.packed(e) for e, _ in up_packed]), p.array([p.packed(o) for _, o in up_packed])
+    w.up_b = p.array([p(u.bias) for u in ups])
+    w.fin_w, w.fin_b, w.fin_g, w.fin_be = p.packed(B.pack_conv(fin[0].weight)), p(fin[0].bias), p(fin[1].weight), p(fin[1].bias)
+    w.out_w, w.out_b = p.packed(fin[3].weight.detach()[:, :, 0]), p(fin[3].bias)
+    if not adds.finish(w, p):
+        return None
+    p.keep.append(arr)
+    return _Bound(w, p.keep, None)
 
 
-def _bind_janner_gemm(net, H: int, device) -> Optional[_Bound]:
-    """Unconditional JannerUNet1d for the same implicit-GEMM executor (bias-only FiLM from Linear(Mish(emb)), no obs half)."""
-    import torch.nn as nn
+def _chiunet_adds(net) -> Optional[SimpleNamespace]:
+    """ChiUNet1d: FiLM from cond_encoder (scale + bias unless cond_predict_scale is off), the observation either as one global
+    vector through global_cond_encoder or -- local conditioning -- as a row per position through two extra residual blocks."""
     from . import blocks as B
+    local = not net.obs_as_global_cond                  # local conditioning: one observation row per position (chiunet.py:78-82)
+    if (local and net.local_cond_encoder is None) or (not local and net.global_cond_encoder is None) or (local and len(net.downs) < 2):
+        return None
+    E = net.emb_dim
+
+    def more_blocks(blocks, bind_block):
+        if not local:
+            return blocks
+        # the two places the local features join have a residual conv in every real net (act_dim != model_dim; concat input)
+        if blocks[0] is None or blocks[0].wra is None or blocks[-2] is None or blocks[-2].wra is None:
+            return None
+        return blocks + [bind_block(net.local_cond_encoder[0]), bind_block(net.local_cond_encoder[1])]
+
+    def finish(w, p):
+        if local:
+            down = net.local_cond_encoder[2].conv
+            w.local_obs_dim = net.local_cond_encoder[0].conv1[0].in_channels
+            w.lc_down_w, w.lc_down_b = p.packed(B.pack_conv(down.weight)), p(down.bias)
+        else:
+            w.gce_w, w.gce_b = p(net.global_cond_encoder.weight), p(net.global_cond_encoder.bias)
+        return True
+
+    header = dict(act_dim=net.downs[0][0].conv1[0].in_channels, emb_dim=E, cond_dim=0 if local else net.global_cond_encoder.in_features,
+                  kernel_size=net.final_conv[0].kernel_size[0], cond_predict_scale=int(net.downs[0][0].cond_predict_scale),
+                  emb_out=E, film_ld=E if local else 2 * E)
+    return SimpleNamespace(film=lambda blk: blk.cond_encoder[1], mids=list(net.mids), norm=None, header=header,
+                           more_blocks=more_blocks, finish=finish)
+
+
+def _janner_adds(net) -> Optional[SimpleNamespace]:
+    """JannerUNet1d: no observation input and bias-only FiLM from Linear(Mish(emb)); GroupNorm1d only; one kernel size for the blocks
+    and the final conv; with ``attention=True`` a LinearAttention after every level's second block and between the middle blocks."""
     from ..utils import GroupNorm1d
-    if H & (H - 1):
-        return None
-    n_levels = len(net.downs)
-    if (H >> (n_levels - 1)) < 1 or n_levels > 8:
-        return None
-    keep = []
-    p = lambda t: _dev_f32(t, keep, device)  # noqa: E731
-
-    def packed(t):
-        t = t.to(device=device, dtype=torch.float32).contiguous()
-        keep.append(t)
-        return t.data_ptr()
-
-    def bind_block(blk, cin_a, cin_b):
-        c1, gn1, c2, gn2 = blk.conv1[0], blk.conv1[1], blk.conv2[0], blk.conv2[1]
-        if not isinstance(gn1, GroupNorm1d) or not isinstance(gn2, GroupNorm1d):
-            return None
-        w1 = B.pack_conv(c1.weight)
-        has_res = isinstance(blk.residual_conv, nn.Conv1d)
-        wr = blk.residual_conv.weight.detach()[:, :, 0] if has_res else None
-        return CdxChiUNetBlock(
-            cin_a=cin_a, cin_b=cin_b, cout=c1.out_channels, groups=gn1.num_groups,
-            w1a=packed(w1[:, :, :cin_a]), w1b=packed(w1[:, :, cin_a:]) if cin_b else None, b1=p(c1.bias), g1=p(gn1.weight),
-            be1=p(gn1.bias), w2=packed(B.pack_conv(c2.weight)), b2=p(c2.bias), g2=p(gn2.weight), be2=p(gn2.bias),
-            film_w=p(blk.emb_mlp[1].weight), film_b=p(blk.emb_mlp[1].bias),
-            wra=packed(wr[:, :cin_a]) if has_res else None, wrb=packed(wr[:, cin_a:]) if (has_res and cin_b) else None,
-            br=p(blk.residual_conv.bias) if has_res else None)
-
-    blocks = []
-    for res1, res2, _, _ in net.downs:
-        blocks += [bind_block(res1, res1.conv1[0].in_channels, 0), bind_block(res2, res2.conv1[0].in_channels, 0)]
-    blocks += [bind_block(m, m.conv1[0].in_channels, 0) for m in (net.mid_block1, net.mid_block2)]
-    for res1, res2, _, _ in net.ups:
-        half = res1.conv1[0].in_channels // 2
-        blocks += [bind_block(res1, half, half), bind_block(res2, res2.conv1[0].in_channels, 0)]
-    if any(b is None for b in blocks):
-        return None
-    for b in blocks:
-        if b.wra is None and (b.cin_b or b.cin_a != b.cout):
-            return None
-    arr = (CdxChiUNetBlock * len(blocks))(*blocks)
-
-    def ptr_array(vals):
-        a = (ctypes.c_void_p * max(len(vals), 1))(*vals)
-        keep.append(a)
-        return a
-    downs = [lvl[3].conv for lvl in net.downs if not isinstance(lvl[3], nn.Identity)]
-    ups = [lvl[3].conv for lvl in net.ups if not isinstance(lvl[3], nn.Identity)]
-    if len(downs) != n_levels - 1 or len(ups) != n_levels - 1:
-        return None
-    up_packed = [B.pack_conv_transpose_k4s2p1(u.weight) for u in ups]
     fin = net.final_conv
-    if not isinstance(fin[1], GroupNorm1d):
+    if not isinstance(fin[1], GroupNorm1d) or fin[0].kernel_size[0] != net.kernel_size:
         return None
-    w = CdxChiUNetWeights()
-    w.act_dim, w.Ta, w.cond_dim, w.emb_dim = net.in_dim, H, 0, net.map_emb[0].in_features
-    w.kernel_size, w.n_levels, w.cond_predict_scale = net.kernel_size, n_levels, 0
-    if fin[0].kernel_size[0] != net.kernel_size:
-        return None                                   # the executor uses one kernel size for the blocks and the final conv
-    w.model_dim, w.final_groups = net.model_dim, fin[1].num_groups
-    w.emb_hidden, w.emb_out, w.film_ld = net.map_emb[0].out_features, net.map_emb[2].out_features, net.map_emb[2].out_features
-    w.map0_w, w.map0_b, w.map2_w, w.map2_b = p(net.map_emb[0].weight), p(net.map_emb[0].bias), p(net.map_emb[2].weight), p(net.map_emb[2].bias)
-    w.gce_w, w.gce_b = None, None
-    w.blocks = arr
-    w.down_w, w.down_b = ptr_array([packed(B.pack_conv(d.weight)) for d in downs]), ptr_array([p(d.bias) for d in downs])
-    w.up_w_even, w.up_w_odd = ptr_array([packed(e) for e, _ in up_packed]), ptr_array([packed(o) for _, o in up_packed])
-    w.up_b = ptr_array([p(u.bias) for u in ups])
-    w.fin_w, w.fin_b, w.fin_g, w.fin_be = packed(B.pack_conv(fin[0].weight)), p(fin[0].bias), p(fin[1].weight), p(fin[1].bias)
-    w.out_w, w.out_b = packed(fin[3].weight.detach()[:, :, 0]), p(fin[3].bias)
-    if getattr(net, "attention", False):
-        # LinearAttention (reference jannerunet.py:72-95) after every level's second block and between the middle blocks: channel
-        # LayerNorm -> to_qkv GEMM -> cdx_linattn_f32 -> to_out GEMM + the normalised input
+
+    def finish(w, p):
+        if not getattr(net, "attention", False):
+            return True
+        # LinearAttention (reference jannerunet.py:72-95): channel LayerNorm -> to_qkv GEMM -> cdx_linattn_f32 -> to_out GEMM + the
+        # normalised input
         from ..nn_diffusion.jannerunet import LinearAttention
         sites = [lvl[2] for lvl in net.downs] + [net.mid_attn] + [lvl[2] for lvl in net.ups]
-        if len(sites) != 2 * n_levels or any(type(a) is not LinearAttention or a.to_qkv.bias is not None for a in sites):
-            return None
+        if len(sites) != 2 * w.n_levels or any(type(a) is not LinearAttention or a.to_qkv.bias is not None for a in sites):
+            return False
         att = (CdxUnetAttn * len(sites))()
         for i, a in enumerate(sites):
             inner = a.to_out.in_channels
             if inner % a.heads or inner // a.heads > 64 or abs(a.scale - (inner // a.heads) ** -0.5) > 1e-12 or abs(a.norm.eps - 1e-5) > 1e-12:
-                return None
+                return False
             att[i] = CdxUnetAttn(p(a.norm.g.reshape(-1)), p(a.norm.b.reshape(-1)), p(a.to_qkv.weight.reshape(a.to_qkv.out_channels, -1)),
                                  p(a.to_out.weight.reshape(a.to_out.out_channels, -1)), p(a.to_out.bias), a.heads, inner // a.heads)
         w.attn = att
-        keep.append(att)
-    keep.append(arr)
-    return _Bound(w, keep, None)
+        p.keep.append(att)
+        return True
+
+    emb_out = net.map_emb[2].out_features
+    header = dict(act_dim=net.in_dim, emb_dim=net.map_emb[0].in_features, cond_dim=0, kernel_size=net.kernel_size, cond_predict_scale=0,
+                  emb_out=emb_out, film_ld=emb_out)
+    return SimpleNamespace(film=lambda blk: blk.emb_mlp[1], mids=[net.mid_block1, net.mid_block2], norm=GroupNorm1d, header=header,
+                           more_blocks=lambda blocks, bind_block: blocks, finish=finish)
 
 
 def _bound(net, key, make) -> Optional[_Bound]:
@@ -557,27 +495,6 @@ def _workspace(device, floats: int) -> torch.Tensor:
     if ws is None or ws.numel() < floats:
         _workspaces[key] = ws = torch.empty(int(floats), dtype=torch.float32, device=device)
     return ws
-
-
-def host_steps(plan):
-    """plan.Step list -> host-resident cdx_step array (the C loop reads it while enqueuing); memoised on the plan."""
-    from .plan import cached
-    return cached(plan, ("host_steps",), lambda: _pack_host_steps(plan))
-
-
-def _pack_host_steps(plan):
-    arr = (CdxStep * max(len(plan.steps), 1))()
-    k = 0
-    for i, st in enumerate(plan.steps):
-        arr[i].kind, arr[i].vsel, arr[i].push, arr[i].flags = st.kind, st.vsel, int(st.push), int(st.flags)
-        arr[i].alpha, arr[i].sigma = st.alpha, st.sigma
-        for j in range(5):
-            arr[i].k[j] = st.k[j]
-        if st.noise:
-            arr[i].noise_idx, k = k, k + 1
-        else:
-            arr[i].noise_idx = -1
-    return arr
 
 
 # Chunk sizes (measured on MI355X, tools/bench_configs.py with CDX_DIT_CHUNK / CDX_MLP_CHUNK): the GEMMs are compute bound, so
@@ -650,164 +567,24 @@ def is_chiunet_gemm(module, batch: int, horizon: Optional[int] = None, edm: bool
     return forward and runtime2.compact_only(module, horizon)       # (compact programs serve sampling loops only)
 
 
-def _bind_unet_gemm(net, tokens: int, dev):
-    from ..nn_diffusion.jannerunet import JannerUNet1d
-    return _bind_janner_gemm(net, tokens, dev) if type(net) is JannerUNet1d else _bind_chiunet(net, tokens, dev)
-
-
 def _chiunet_chunk(batch: int, Ta: int, model_dim: int, two: int) -> int:
     rows = max((256 << 20) // (4 * model_dim), 4096)       # widest live activation ~ rows x model_dim
     return max(min(batch, rows // (Ta * two)), 1)
 
 
-def janner_forward(net, x, noise, condition=None) -> Optional[torch.Tensor]:
-    """JannerUNet1d.forward with per-sample timesteps through the implicit-GEMM executor (what a guided / custom loop calls once per
-    step when the net is too large for the one-workgroup program kernel, and ``attention=True`` nets at every size).  A condition
-    embedding enters the time embedding BEFORE map_emb (reference jannerunet.py:160-164: emb = map_noise(t) + condition), so a
-    conditional forward is the same launch on the per-sample rows map_noise(t) + condition (round 5: conditional attention nets)."""
-    if x.dim() != 3 or (condition is not None and (condition.dim() != 2 or condition.shape[0] != x.shape[0])):
-        return None
-    dev = x.device
-    b, H, d = x.shape
-    bound = _bound(net, ("chiunet", H), lambda: _bind_janner_gemm(net, H, dev))
-    if bound is None or d != bound.struct.act_dim:
-        return None
-    w = bound.struct
-    with torch.no_grad():
-        temb = net.map_noise(noise)
-        if condition is not None:
-            if tuple(condition.shape) != (b, temb.shape[-1]):
-                return None
-            temb = temb.expand(b, -1) + condition
-        temb = _f32c(temb.expand(b, -1), dev)
-        xin = _f32c(x, dev)
-        out = torch.empty_like(xin)
-        _run("chiunet", bound, batch=b, hd=H * d, emb_dim=w.emb_dim, cond_dim=0, temb=temb, steps=None, n_steps=0,
-             temb_per_sample=1, predict_noise=0, cfg_mode=0, cfg_w=0.0, cond=None, x_in=xin, prior=None, fix_mask=None,
-             noise=None, x_min=None, x_max=None, x_out=out,
-             chunk=CHUNK_OVERRIDE["chiunet"] or _chiunet_chunk(b, H, net.model_dim if hasattr(net, "model_dim") else 32, 1))
-    return out
+def unet_chunk(net, batch: int, length: int, two: int = 1) -> int:
+    """Trajectories per pass of the U-Net executor (CDX_CHIUNET_CHUNK / CHUNK_OVERRIDE["chiunet"] overrides the rule)."""
+    return CHUNK_OVERRIDE["chiunet"] or _chiunet_chunk(batch, length, getattr(net, "model_dim", 32), two)
+
+
+def unet_binding(net, length: int, device) -> Optional[_Bound]:
+    """The U-Net executor's weights of `net` at this length: the binding sample() / forward() use, shared with the guided loop."""
+    return _bound(net, ("chiunet", length), lambda: _bind_unet(net, length, device))
 
 
 def _unet_cond_dim(w) -> int:
     """Width of a request's flattened condition: To * obs_dim (global conditioning) or Ta * obs_dim (local: a row per position)."""
     return w.Ta * w.local_obs_dim if w.local_obs_dim > 0 else w.cond_dim
-
-
-def chiunet_forward(net, x, noise, condition) -> Optional[torch.Tensor]:
-    from ..nn_diffusion.jannerunet import JannerUNet1d
-    if type(net) is JannerUNet1d:
-        return janner_forward(net, x, noise, condition)
-    if x.dim() != 3 or condition is None:
-        return None
-    dev = x.device
-    b, Ta, _ = x.shape
-    bound = _bound(net, ("chiunet", Ta), lambda: _bind_chiunet(net, Ta, dev))
-    if bound is None or x.shape[2] != bound.struct.act_dim:
-        return None
-    w = bound.struct
-    with torch.no_grad():
-        cond = _f32c(torch.flatten(condition, 1), dev)
-        cond_dim = _unet_cond_dim(w)
-        if cond.shape[1] != cond_dim:
-            return None
-        temb = _f32c(net.map_noise(noise), dev)
-        xin = _f32c(x, dev)
-        out = torch.empty_like(xin)
-        _run("chiunet", bound, batch=b, hd=Ta * w.act_dim, emb_dim=w.emb_dim, cond_dim=cond_dim, temb=temb, steps=None,
-             n_steps=0, temb_per_sample=1, predict_noise=0, cfg_mode=1, cfg_w=1.0, cond=cond, x_in=xin, prior=None,
-             fix_mask=None, noise=None, x_min=None, x_max=None, x_out=out,
-             chunk=CHUNK_OVERRIDE["chiunet"] or _chiunet_chunk(b, Ta, net.model_dim, 1))
-    return out
-
-
-def _run(kind, bound, *, batch, hd, emb_dim, cond_dim, temb, steps, n_steps, temb_per_sample, predict_noise, cfg_mode,
-         cfg_w, cond, x_in, prior, fix_mask, noise, x_min, x_max, x_out, chunk):
-    lib = _lib()
-    pp = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    s = CdxSampling(batch=batch, hd=hd, emb_dim=emb_dim, cond_dim=cond_dim, temb=temb.data_ptr(), steps=steps,
-                    n_steps=n_steps, temb_per_sample=int(temb_per_sample), predict_noise=int(predict_noise),
-                    cfg_mode=cfg_mode, cfg_w=float(cfg_w), cond=pp(cond), x_in=x_in.data_ptr(), prior=pp(prior),
-                    fix_mask=pp(fix_mask), noise=pp(noise), x_min=pp(x_min), x_max=pp(x_max), x_out=x_out.data_ptr(),
-                    workspace=None, workspace_floats=0, chunk=chunk)
-    size_fn, run_fn = {"dit": (lib.cdx_dit1d_workspace_floats, lib.cdx_dit1d_run),
-                       "pearcetf": (lib.cdx_pearcetf_workspace_floats, lib.cdx_pearcetf_run),
-                       "mlp": (lib.cdx_resmlp_workspace_floats, lib.cdx_resmlp_run),
-                       "chitf": (lib.cdx_chitf_workspace_floats, lib.cdx_chitf_run),
-                       "chiunet": (lib.cdx_chiunet_workspace_floats, lib.cdx_chiunet_run)}[kind]
-    need = size_fn(ctypes.byref(bound.struct), ctypes.byref(s))
-    ws = _workspace(x_in.device, need)
-    s.workspace, s.workspace_floats = ws.data_ptr(), ws.numel()
-    if batch:
-        _check(run_fn(ctypes.byref(bound.struct), ctypes.byref(s), _stream_ptr(x_in.device)), f"cdx_{kind}_run")
-
-
-# ------------------------------------------------------------------------------------------------ #
-# backbone.forward                                                                                     #
-# ------------------------------------------------------------------------------------------------ #
-def pearcetf_forward(net, x, noise, condition) -> Optional[torch.Tensor]:
-    if x.dim() != 2 or condition is None or condition.dim() != 3:
-        return None
-    if net.training:
-        # train mode: BatchNorm1d uses batch statistics (reference pearcetransformer.py:38-39) -- the folded eval-mode weights a cached
-        # binding holds do not describe that network (the cache key is the weight signature, not the mode: ADVICE r3)
-        return None
-    dev = x.device
-    bound = _bound(net, "pearcetf", lambda: _bind_pearcetf(net, dev))
-    if bound is None or x.shape[1] != bound.struct.act_dim or tuple(condition.shape[1:]) != (net.To, net.emb_dim):
-        return None
-    w = bound.struct
-    with torch.no_grad():
-        temb = _f32c(net.map_noise(noise), dev)
-        cond = _f32c(torch.flatten(condition, 1), dev)
-        xin = _f32c(x, dev)
-        out = torch.empty_like(xin)
-        _run("pearcetf", bound, batch=x.shape[0], hd=w.act_dim, emb_dim=w.emb_dim, cond_dim=w.To * w.emb_dim, temb=temb, steps=None,
-             n_steps=0, temb_per_sample=1, predict_noise=0, cfg_mode=1, cfg_w=1.0, cond=cond, x_in=xin, prior=None, fix_mask=None,
-             noise=None, x_min=None, x_max=None, x_out=out, chunk=CHUNK_OVERRIDE["dit"] or _dit_chunk(x.shape[0], 2 + w.To, w.te * w.n_heads, 1))
-    return out
-
-
-def dit_forward(net, x, noise, condition) -> Optional[torch.Tensor]:
-    if x.dim() != 3 or x.shape[2] != net.in_dim * (2 if is_dit1ref(net) else 1):
-        return None
-    b, tokens, _ = x.shape
-    dev = x.device
-    bound = _bound(net, ("dit", tokens), lambda: _bind_dit(net, tokens, dev))
-    if bound is None:
-        return None
-    with torch.no_grad():
-        temb = _f32c(net.map_noise(noise), dev)
-        cond = None if condition is None else _f32c(condition, dev)
-        xin = _f32c(x, dev)
-        out = torch.empty_like(xin)
-        _run("dit", bound, batch=b, hd=tokens * x.shape[2], emb_dim=net.emb_dim, cond_dim=net.emb_dim, temb=temb,
-             steps=None, n_steps=0, temb_per_sample=1, predict_noise=0, cfg_mode=1 if cond is not None else 0, cfg_w=1.0,
-             cond=cond, x_in=xin, prior=None, fix_mask=None, noise=None, x_min=None, x_max=None, x_out=out,
-             chunk=CHUNK_OVERRIDE["dit"] or _dit_chunk(b, tokens, net.d_model, 1))
-    return out
-
-
-def chitf_forward(net, x, noise, condition) -> Optional[torch.Tensor]:
-    if x.dim() != 3 or x.shape[1] != net.T:
-        return None
-    dev = x.device
-    bound = _bound(net, "chitf", lambda: _bind_chitf(net, dev))
-    if bound is None or x.shape[2] != bound.struct.act_dim:
-        return None
-    w = bound.struct
-    with torch.no_grad():
-        temb = _f32c(net.map_noise(noise), dev)
-        cond = None if condition is None else _f32c(torch.flatten(condition, 1), dev)
-        if cond is not None and cond.shape[1] != w.To * w.obs_dim:
-            return None
-        xin = _f32c(x, dev)
-        out = torch.empty_like(xin)
-        _run("chitf", bound, batch=x.shape[0], hd=w.Ta * w.act_dim, emb_dim=w.d_model, cond_dim=w.To * w.obs_dim, temb=temb,
-             steps=None, n_steps=0, temb_per_sample=1, predict_noise=0, cfg_mode=1 if cond is not None else 0, cfg_w=1.0,
-             cond=cond, x_in=xin, prior=None, fix_mask=None, noise=None, x_min=None, x_max=None, x_out=out,
-             chunk=CHUNK_OVERRIDE["chitf"] or _dit_chunk(x.shape[0], w.Ta, w.d_model, 1))
-    return out
 
 
 def _time_features(net, t_vec, dev) -> torch.Tensor:
@@ -819,23 +596,140 @@ def _time_features(net, t_vec, dev) -> torch.Tensor:
     return blocks.linear(h, _f32c(l2.weight, dev), _f32c(l2.bias, dev))
 
 
-def resmlp_forward(net, x, noise, condition) -> Optional[torch.Tensor]:
-    if x.dim() != 2:
+# ------------------------------------------------------------------------------------------------ #
+# the backbone families                                                                                #
+# ------------------------------------------------------------------------------------------------ #
+class Family(NamedTuple):
+    """Everything the host path knows about one backbone family.  ``w`` below is the bound weight struct."""
+    kind: str                        # name in _run and in the binding cache: `kind`, or (`kind`, length) where `per_length`
+    entry: str                       # the C entries are cdx_<entry>_workspace_floats / cdx_<entry>_run ...
+    weights: type                    # ... and take this struct
+    modules: tuple                   # "file.Class" under nn_diffusion: the exact types served
+    bind: Callable                   # (net, length, device) -> _Bound | None
+    length: Optional[str]            # None: the state is (b, d).  Else it is (b, length, d) and this field of w holds the length
+    width: Callable                  # w -> what the state's last dimension must equal
+    cond_dim: Callable               # w -> width of a flattened condition row (0: the family takes no condition input)
+    chunk: Callable                  # (net, w, batch, two) -> samples per pass; CHUNK_OVERRIDE[`override`] goes first
+    override: str
+    per_length: bool = False         # the binding depends on the length (position tables, level sizes)
+    emb: str = "emb_dim"             # field of w with the width of a time-embedding row
+    temb: Callable = lambda net, t, dev: _f32c(net.map_noise(t), dev)      # one embedding row per timestep
+    # "optional"; "required" (the reference cannot run the net without one); "embedding": no condition input, forward() adds the
+    # condition to map_noise(t) in front of map_emb (reference jannerunet.py:160-164) and sample() declines conditional requests
+    cond: str = "optional"
+    cond_shape: Optional[Callable] = None     # w -> shape[1:] the unflattened condition must have
+    forward_checks_cond: bool = True          # forward() of DiT1d / IDQLMlp passes the condition on as it comes; sample() always checks
+    refuses: Callable = lambda net: False     # asked before the binding cache is
+
+
+FAMILIES = (
+    Family("dit", "dit1d", CdxDitWeights, ("dit.DiT1d", "dit.DiT1Ref"), _bind_dit, "tokens", per_length=True,
+           width=lambda w: w.in_dim * (2 if w.cross else 1),             # DiT1Ref rows are [reference | noisy]
+           cond_dim=lambda w: w.emb_dim, forward_checks_cond=False,
+           chunk=lambda net, w, b, two: _dit_chunk(b, w.tokens, w.d_model, two), override="dit"),
+    # PearceTransformer runs 2 + To tokens of te * n_heads features per sample through the DiT kernels: DiT's chunk rule and override.
+    # Train mode: BatchNorm1d uses batch statistics (reference pearcetransformer.py:38-39) -- the folded eval-mode weights a cached
+    # binding holds do not describe that network (the cache key is the weight signature, not the mode)
+    Family("pearcetf", "pearcetf", CdxPearcetfWeights, ("pearcetransformer.PearceTransformer",), _bind_pearcetf, None,
+           width=lambda w: w.act_dim, cond_dim=lambda w: w.To * w.emb_dim, cond="required", cond_shape=lambda w: (w.To, w.emb_dim),
+           chunk=lambda net, w, b, two: _dit_chunk(b, 2 + w.To, w.te * w.n_heads, two), override="dit",
+           refuses=lambda net: net.training),
+    Family("chitf", "chitf", CdxChitfWeights, ("chitransformer.ChiTransformer",), _bind_chitf, "Ta", emb="d_model",
+           width=lambda w: w.act_dim, cond_dim=lambda w: w.To * w.obs_dim,
+           chunk=lambda net, w, b, two: _dit_chunk(b, w.Ta, w.d_model, two), override="chitf"),
+    Family("mlp", "resmlp", CdxResMlpWeights, ("mlp_backbones.IDQLMlp", "mlp_backbones.NewIDQLMlp"), _bind_resmlp, None,
+           width=lambda w: w.x_dim, cond_dim=lambda w: w.obs_dim, forward_checks_cond=False,
+           temb=lambda net, t, dev: _time_features(net, t, dev),         # its rows are time_mlp(map_noise(t))
+           chunk=lambda net, w, b, two: _mlp_chunk(b, w.hidden, two), override="mlp"),
+    # the two U-Nets share the executor, its struct and one binding cache; dispatch asks is_chiunet_gemm before it offers them a request
+    _CHIUNET := Family("chiunet", "chiunet", CdxChiUNetWeights, ("chiunet.ChiUNet1d",), _bind_unet, "Ta", per_length=True,
+                       width=lambda w: w.act_dim, cond_dim=_unet_cond_dim, cond="required",
+                       chunk=lambda net, w, b, two: _chiunet_chunk(b, w.Ta, getattr(net, "model_dim", 32), two), override="chiunet"),
+    _CHIUNET._replace(modules=("jannerunet.JannerUNet1d",), cond="embedding"),
+)
+_ENTRY = {fam.kind: fam.entry for fam in FAMILIES}
+
+
+@functools.lru_cache(None)
+def _served_types() -> dict:
+    return {getattr(importlib.import_module("..nn_diffusion." + path.split(".")[0], __package__), path.split(".")[1]): fam
+            for fam in FAMILIES for path in fam.modules}
+
+
+def family_of(module) -> Optional[Family]:
+    """The family serving exactly this module type (subclasses may compute something else), or None."""
+    return _served_types().get(type(module))
+
+
+def _run(kind, bound, *, batch, hd, emb_dim, cond_dim, temb, steps, n_steps, temb_per_sample, predict_noise, cfg_mode,
+         cfg_w, cond, x_in, prior, fix_mask, noise, x_min, x_max, x_out, chunk):
+    lib = _lib()
+    pp = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    s = CdxSampling(batch=batch, hd=hd, emb_dim=emb_dim, cond_dim=cond_dim, temb=temb.data_ptr(), steps=steps,
+                    n_steps=n_steps, temb_per_sample=int(temb_per_sample), predict_noise=int(predict_noise),
+                    cfg_mode=cfg_mode, cfg_w=float(cfg_w), cond=pp(cond), x_in=x_in.data_ptr(), prior=pp(prior),
+                    fix_mask=pp(fix_mask), noise=pp(noise), x_min=pp(x_min), x_max=pp(x_max), x_out=x_out.data_ptr(),
+                    workspace=None, workspace_floats=0, chunk=chunk)
+    size_fn, run_fn = getattr(lib, f"cdx_{_ENTRY[kind]}_workspace_floats"), getattr(lib, f"cdx_{_ENTRY[kind]}_run")
+    need = size_fn(ctypes.byref(bound.struct), ctypes.byref(s))
+    ws = _workspace(x_in.device, need)
+    s.workspace, s.workspace_floats = ws.data_ptr(), ws.numel()
+    if batch:
+        _check(run_fn(ctypes.byref(bound.struct), ctypes.byref(s), _stream_ptr(x_in.device)), f"cdx_{kind}_run")
+
+
+def _binding(fam, net, x) -> Optional[_Bound]:
+    """The weights of `net` for a state shaped like `x`, or None when the family's executor does not take it."""
+    if x.dim() != (3 if fam.length else 2) or fam.refuses(net):
         return None
-    dev = x.device
-    bound = _bound(net, "mlp", lambda: _bind_resmlp(net, dev))
-    if bound is None or x.shape[1] != bound.struct.x_dim:
+    length = x.shape[1] if fam.length else None
+    bound = _bound(net, (fam.kind, length) if fam.per_length else fam.kind, lambda: fam.bind(net, length, x.device))
+    if bound is None or x.shape[-1] != fam.width(bound.struct) or (fam.length and length != getattr(bound.struct, fam.length)):
         return None
+    return bound
+
+
+def _condition_rows(fam, w, cond, dev, check_width=True) -> Optional[torch.Tensor]:
+    """A condition flattened to fp32 rows, or None when its shape is not what the family takes."""
+    if fam.cond_shape is not None and tuple(cond.shape[1:]) != fam.cond_shape(w):
+        return None
+    rows = _f32c(torch.flatten(cond, 1), dev)
+    return rows if not check_width or rows.shape[1] == fam.cond_dim(w) else None
+
+
+# ------------------------------------------------------------------------------------------------ #
+# backbone.forward                                                                                     #
+# ------------------------------------------------------------------------------------------------ #
+def forward(net, x, noise, condition=None) -> Optional[torch.Tensor]:
+    """``backbone.forward`` with a timestep per sample (what training-time evaluation, guided and custom loops call) as one executor
+    call.  None -> the request is not one for this executor."""
+    fam = family_of(net)
+    if fam is None or (fam.cond == "required" and condition is None):
+        return None
+    bound = _binding(fam, net, x)
+    if bound is None:
+        return None
+    w, b, dev = bound.struct, x.shape[0], x.device
     with torch.no_grad():
-        temb = _time_features(net, noise, dev)
-        cond = None if (condition is None or net.obs_dim == 0) else _f32c(condition, dev)
+        temb, cond = fam.temb(net, noise, dev), None
+        if fam.cond == "embedding":
+            temb = temb.expand(b, -1)
+            if condition is not None:
+                if tuple(condition.shape) != tuple(temb.shape):
+                    return None
+                temb = temb + condition
+            temb = _f32c(temb, dev)
+        elif condition is not None and fam.cond_dim(w) > 0:
+            cond = _condition_rows(fam, w, condition, dev, fam.forward_checks_cond)
+            if cond is None:
+                return None
         xin = _f32c(x, dev)
         out = torch.empty_like(xin)
-        w = bound.struct
-        _run("mlp", bound, batch=x.shape[0], hd=w.x_dim, emb_dim=w.emb_dim, cond_dim=w.obs_dim, temb=temb, steps=None,
-             n_steps=0, temb_per_sample=1, predict_noise=0, cfg_mode=1 if cond is not None else 0, cfg_w=1.0, cond=cond,
-             x_in=xin, prior=None, fix_mask=None, noise=None, x_min=None, x_max=None, x_out=out,
-             chunk=CHUNK_OVERRIDE["mlp"] or _mlp_chunk(x.shape[0], w.hidden, 1))
+        _run(fam.kind, bound, batch=b, hd=(x.shape[1] if fam.length else 1) * x.shape[-1], emb_dim=getattr(w, fam.emb),
+             cond_dim=fam.cond_dim(w), temb=temb, steps=None, n_steps=0, temb_per_sample=1, predict_noise=0,
+             cfg_mode=1 if cond is not None else 0, cfg_w=0.0 if fam.cond == "embedding" else 1.0, cond=cond, x_in=xin, prior=None,
+             fix_mask=None, noise=None, x_min=None, x_max=None, x_out=out,
+             chunk=CHUNK_OVERRIDE[fam.override] or fam.chunk(net, w, b, 1))
     return out
 
 
@@ -843,59 +737,22 @@ def resmlp_forward(net, x, noise, condition) -> Optional[torch.Tensor]:
 # sample()                                                                                             #
 # ------------------------------------------------------------------------------------------------ #
 def sample(solver, net, plan, xt, prior, cond_vec, w_cfg, feed) -> Optional[torch.Tensor]:
-    """Whole denoising loop through cdx_dit1d_run / cdx_resmlp_run.  None -> caller uses the PyTorch executor."""
-    dev = xt.device
-    if is_pearcetf(net):
-        if xt.dim() != 2 or cond_vec is None or w_cfg == 0.0 or cond_vec.dim() != 3:
-            return None                               # (the reference cannot run this backbone without a condition either)
-        kind, (b, d) = "pearcetf", xt.shape
-        if net.training:                 # (see pearcetf_forward: sample(use_ema=False) on a module in train mode)
-            return None
-        bound = _bound(net, "pearcetf", lambda: _bind_pearcetf(net, dev))
-        hd, rows_h = d, 1
-        if bound is not None and (bound.struct.act_dim != d or tuple(cond_vec.shape[1:]) != (net.To, net.emb_dim)):
-            return None
-    elif is_dit1d(net) or is_dit1ref(net):
-        if xt.dim() != 3 or xt.shape[2] != net.in_dim * (2 if is_dit1ref(net) else 1):
-            return None
-        kind, (b, tokens, d) = "dit", xt.shape
-        bound = _bound(net, ("dit", tokens), lambda: _bind_dit(net, tokens, dev))
-        hd, rows_h = tokens * d, tokens
-    elif is_chiunet_gemm(net, xt.shape[0], xt.shape[1] if xt.dim() == 3 else None, runtime.plan_is_edm(plan)):
-        from ..nn_diffusion.jannerunet import JannerUNet1d
-        janner = type(net) is JannerUNet1d
-        if xt.dim() != 3 or (janner and cond_vec is not None and w_cfg != 0.0) or \
-                (not janner and (cond_vec is None or w_cfg == 0.0)):
-            return None                               # ChiUNet1d needs a condition (the reference raises); Janner here: none
-        if janner:
-            cond_vec = None
-        kind, (b, tokens, d) = "chiunet", xt.shape
-        bound = _bound(net, ("chiunet", tokens), lambda: _bind_unet_gemm(net, tokens, dev))
-        hd, rows_h = tokens * d, tokens
-        if bound is not None and bound.struct.act_dim != d:
-            return None
-    elif is_chitf(net):
-        if xt.dim() != 3 or xt.shape[1] != net.T:
-            return None
-        kind, (b, tokens, d) = "chitf", xt.shape
-        bound = _bound(net, "chitf", lambda: _bind_chitf(net, dev))
-        hd, rows_h = tokens * d, tokens
-        if bound is not None and bound.struct.act_dim != d:
-            return None
-    elif is_resmlp(net):
-        if xt.dim() != 2:
-            return None
-        kind, (b, d) = "mlp", xt.shape
-        bound = _bound(net, "mlp", lambda: _bind_resmlp(net, dev))
-        hd, rows_h = d, 1
-        if bound is not None and bound.struct.x_dim != d:
-            return None
-    else:
+    """Whole denoising loop as one executor call.  None -> caller uses another executor; no noise has been drawn from `feed` then."""
+    fam = family_of(net)
+    if fam is None:
         return None
+    conditional = cond_vec is not None and w_cfg != 0.0
+    if (fam.cond == "required" and not conditional) or (fam.cond == "embedding" and conditional):
+        return None                                   # (the reference cannot run those backbones without a condition either)
+    if fam.cond == "embedding":
+        cond_vec = None
+    bound = _binding(fam, net, xt)
     if bound is None:
         return None
     if cond_vec is None and w_cfg not in (0.0, 1.0):
         return None                                   # the reference raises here; let the torch executor do it
+    w, dev, b, d = bound.struct, xt.device, xt.shape[0], xt.shape[-1]
+    rows_h = xt.shape[1] if fam.length else 1
     try:
         fix_mask = _dense_hd(solver.fix_mask, rows_h, d, dev)
         clip = getattr(plan, "clip_each_step", True)
@@ -904,39 +761,19 @@ def sample(solver, net, plan, xt, prior, cond_vec, w_cfg, feed) -> Optional[torc
     except (ValueError, RuntimeError):
         return None
     with torch.no_grad():
-        t_vec = runtime.device_times(plan, dev)
-        if kind == "dit":
-            temb, emb_dim, cond_dim = _f32c(net.map_noise(t_vec), dev), net.emb_dim, net.emb_dim
-        elif kind == "pearcetf":
-            temb, emb_dim, cond_dim = _f32c(net.map_noise(t_vec), dev), net.emb_dim, net.To * net.emb_dim
-        elif kind == "chitf":
-            temb, emb_dim = _f32c(net.map_noise(t_vec), dev), bound.struct.d_model
-            cond_dim = bound.struct.To * bound.struct.obs_dim
-        elif kind == "chiunet":
-            temb, emb_dim, cond_dim = _f32c(net.map_noise(t_vec), dev), bound.struct.emb_dim, _unet_cond_dim(bound.struct)
-        else:
-            temb, emb_dim, cond_dim = _time_features(net, t_vec, dev), bound.struct.emb_dim, bound.struct.obs_dim
-        if cond_vec is None or w_cfg == 0.0 or (kind == "mlp" and cond_dim == 0):
+        temb, cond_dim = fam.temb(net, runtime.device_times(plan, dev), dev), fam.cond_dim(w)
+        if not conditional or cond_dim == 0:
             mode, cond = 0, None
         else:
-            mode, cond = (1 if w_cfg == 1.0 else 2), _f32c(torch.flatten(cond_vec, 1), dev)
-            if cond.shape != (b, cond_dim):
+            mode, cond = (1 if w_cfg == 1.0 else 2), _condition_rows(fam, w, cond_vec, dev)
+            if cond is None or cond.shape[0] != b:
                 return None
-        two = 2 if mode == 2 else 1
-        steps = host_steps(plan)
         noise = feed.many(xt, plan.n_noise)
         xin = _f32c(xt, dev)
         out = torch.empty_like(xin)
-        if kind == "mlp":
-            chunk = CHUNK_OVERRIDE[kind] or _mlp_chunk(b, bound.struct.hidden, two)
-        elif kind == "chiunet":
-            chunk = CHUNK_OVERRIDE[kind] or _chiunet_chunk(b, rows_h, bound.struct.model_dim, two)
-        elif kind == "pearcetf":
-            chunk = CHUNK_OVERRIDE["dit"] or _dit_chunk(b, 2 + bound.struct.To, bound.struct.te * bound.struct.n_heads, two)
-        else:
-            chunk = CHUNK_OVERRIDE[kind] or _dit_chunk(b, rows_h, bound.struct.d_model, two)
-        _run(kind, bound, batch=b, hd=hd, emb_dim=emb_dim, cond_dim=cond_dim, temb=temb, steps=steps,
+        _run(fam.kind, bound, batch=b, hd=rows_h * d, emb_dim=getattr(w, fam.emb), cond_dim=cond_dim, temb=temb, steps=host_steps(plan),
              n_steps=len(plan.steps), temb_per_sample=0, predict_noise=_predicts_noise(plan, solver),
              cfg_mode=mode, cfg_w=w_cfg, cond=cond, x_in=xin, prior=_f32c(prior, dev) if fix_mask is not None else None,
-             fix_mask=fix_mask, noise=noise, x_min=x_min, x_max=x_max, x_out=out, chunk=chunk)
+             fix_mask=fix_mask, noise=noise, x_min=x_min, x_max=x_max, x_out=out,
+             chunk=CHUNK_OVERRIDE[fam.override] or fam.chunk(net, w, b, 2 if mode == 2 else 1))
     return out

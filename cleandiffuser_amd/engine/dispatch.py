@@ -18,6 +18,18 @@ def _on_gpu(t: torch.Tensor) -> bool:
     return t.is_cuda
 
 
+def _gemm_executor(net, x, edm=False, forward=False, unet_only=False):
+    """The big-batch GEMM executor (a bigbatch.Family) this request is to be offered to, or None.  DiT1d / DiT1Ref, PearceTransformer,
+    ChiTransformer and IDQLMlp / NewIDQLMlp have no other native executor: what bigbatch answers is final, None (-> PyTorch) included.
+    The U-Nets (kind "chiunet") also have the program kernel: they are offered from their crossover up (bigbatch.is_chiunet_gemm) and
+    a None leaves the request to that kernel.  (The type sets are disjoint, so it does not matter which of the two is looked at first.)"""
+    from . import bigbatch
+    fam = bigbatch.family_of(net)
+    if fam is None or fam.kind != "chiunet":
+        return None if unet_only else fam
+    return fam if bigbatch.is_chiunet_gemm(net, x.shape[0], x.shape[1] if x.dim() == 3 else None, edm, forward) else None
+
+
 def _try_backbone_forward(module, x, noise, condition) -> Optional[torch.Tensor]:
     """Serve ``backbone.forward`` from the fused program kernel, or return None for the PyTorch path."""
     if not _on_gpu(x) or torch.is_grad_enabled() and _needs_grad(module, x, condition):
@@ -25,17 +37,10 @@ def _try_backbone_forward(module, x, noise, condition) -> Optional[torch.Tensor]
     if x.dtype != torch.float32:
         return None
     from . import bigbatch, runtime
-    if bigbatch.is_dit1d(module) or bigbatch.is_dit1ref(module):
-        return bigbatch.dit_forward(module, x, noise, condition)
-    if bigbatch.is_pearcetf(module):
-        return bigbatch.pearcetf_forward(module, x, noise, condition)
-    if bigbatch.is_resmlp(module):
-        return bigbatch.resmlp_forward(module, x, noise, condition)
-    if bigbatch.is_chitf(module):
-        return bigbatch.chitf_forward(module, x, noise, condition)
-    if bigbatch.is_chiunet_gemm(module, x.shape[0], x.shape[1] if x.dim() == 3 else None, forward=True):
-        y = bigbatch.chiunet_forward(module, x, noise, condition)
-        if y is not None:
+    fam = _gemm_executor(module, x, forward=True)
+    if fam is not None:
+        y = bigbatch.forward(module, x, noise, condition)
+        if y is not None or fam.kind != "chiunet":
             return y
     return runtime.backbone_forward(module, x, noise, condition)
 
@@ -46,6 +51,18 @@ def _needs_grad(module, x, condition) -> bool:
     return any(p.requires_grad for p in module.parameters())
 
 
+def _sample_unguided(solver, model, plan, xt, prior, cond_vec, w_cfg, feed, unet_only=False):
+    """The whole loop on the GEMM executors (EDM / consistency kinds included), else in one launch of the program kernel."""
+    from . import bigbatch, runtime
+    net = model["diffusion"]
+    fam = _gemm_executor(net, xt, edm=runtime.plan_is_edm(plan), unet_only=unet_only)
+    if fam is not None:
+        out = bigbatch.sample(solver, net, plan, xt, prior, cond_vec, w_cfg, feed)
+        if out is not None or fam.kind != "chiunet":
+            return out
+    return runtime.fused_sample(solver, model, plan, xt, prior, cond_vec, w_cfg, feed)
+
+
 def _try_fused_sample(solver, model, plan, xt, prior, cond_vec, w_cfg, w_cg, requires_grad, feed):
     """Run the whole denoising loop in one launch, or return None for the PyTorch executor."""
     if not _on_gpu(xt) or requires_grad or xt.dtype != torch.float32:
@@ -53,15 +70,7 @@ def _try_fused_sample(solver, model, plan, xt, prior, cond_vec, w_cfg, w_cg, req
     if w_cg != 0.0 and solver.classifier is not None:
         from . import guided             # classifier guidance: fused backbone forward + explicit classifier backward per step
         return guided.guided_sample(solver, model, plan, xt, prior, cond_vec, w_cfg, w_cg, feed)
-    from . import bigbatch, runtime
-    net = model["diffusion"]
-    if bigbatch.is_chiunet_gemm(net, xt.shape[0], xt.shape[1] if xt.dim() == 3 else None, runtime.plan_is_edm(plan)):
-        out = bigbatch.sample(solver, net, plan, xt, prior, cond_vec, w_cfg, feed)
-        if out is not None:
-            return out
-    if bigbatch.is_dit1d(net) or bigbatch.is_resmlp(net) or bigbatch.is_chitf(net) or bigbatch.is_dit1ref(net) or bigbatch.is_pearcetf(net):
-        return bigbatch.sample(solver, net, plan, xt, prior, cond_vec, w_cfg, feed)     # EDM / consistency kinds included
-    return runtime.fused_sample(solver, model, plan, xt, prior, cond_vec, w_cfg, feed)
+    return _sample_unguided(solver, model, plan, xt, prior, cond_vec, w_cfg, feed)
 
 
 def _try_fused_raw(solver, model, plan, z, temperature, prior, feed):
@@ -71,14 +80,11 @@ def _try_fused_raw(solver, model, plan, z, temperature, prior, feed):
     None -> the caller forms x_T with ATen ops and goes through try_fused_sample as before (no draw consumed here)."""
     if not _on_gpu(z) or z.dtype != torch.float32 or z.dim() != 3:
         return None
-    from . import bigbatch, runtime
+    from . import runtime, runtime2
     net = model["diffusion"]
-    if not runtime._is_janner(net) or runtime.plan_is_edm(plan):
+    if not runtime._is_janner(net) or runtime.plan_is_edm(plan) or runtime2.supported(net, z.shape[1]) is not None:
         return None
-    from . import runtime2
-    if runtime2.supported(net, z.shape[1]) is not None:
-        return None
-    if bigbatch.is_chiunet_gemm(net, z.shape[0], z.shape[1], False):
+    if _gemm_executor(net, z) is not None:              # (a request the GEMM executor takes starts from x_T)
         return None
     return runtime.fused_sample(solver, model, plan, z, prior, None, 0.0, feed, x_scale=float(temperature))
 
@@ -92,29 +98,17 @@ def _try_fused_edm(solver, model, plan, xt, prior, cond_vec, w_cfg, w_cg, requir
     if w_cg != 0.0 and solver.classifier is not None and condition_cg is not None:
         from . import guided
         return guided.guided_sample(solver, model, plan, xt, prior, cond_vec, w_cfg, w_cg, feed)
-    from . import bigbatch, runtime
-    net = model["diffusion"]
-    if bigbatch.is_resmlp(net) or bigbatch.is_dit1d(net) or bigbatch.is_chitf(net) or bigbatch.is_dit1ref(net) or bigbatch.is_pearcetf(net):
-        return bigbatch.sample(solver, net, plan, xt, prior, cond_vec, w_cfg, feed)
-    if bigbatch.is_chiunet_gemm(net, xt.shape[0], xt.shape[1] if xt.dim() == 3 else None, runtime.plan_is_edm(plan)):
-        out = bigbatch.sample(solver, net, plan, xt, prior, cond_vec, w_cfg, feed)
-        if out is not None:
-            return out
-    return runtime.fused_sample(solver, model, plan, xt, prior, cond_vec, w_cfg, feed)
+    return _sample_unguided(solver, model, plan, xt, prior, cond_vec, w_cfg, feed)
 
 
 def _try_fused_legacy_ddpm(solver, model, plan, xt, prior, cond_vec, w_cfg, w_cg, requires_grad, feed):
-    """Legacy ``DDPM`` class: same fused executor, legacy step kinds."""
+    """Legacy ``DDPM`` class: same fused executor, legacy step kinds.  Of the GEMM executors only the U-Net one is offered: a legacy
+    DDPM over DiT1d or IDQLMlp runs on the PyTorch executor."""
     if not _on_gpu(xt) or requires_grad or xt.dtype != torch.float32:
         return None
     if solver.classifier is not None and w_cg != 0.0:
         return None
-    from . import bigbatch, runtime
-    if bigbatch.is_chiunet_gemm(model["diffusion"], xt.shape[0], xt.shape[1] if xt.dim() == 3 else None, runtime.plan_is_edm(plan)):
-        out = bigbatch.sample(solver, model["diffusion"], plan, xt, prior, cond_vec, w_cfg, feed)
-        if out is not None:
-            return out
-    return runtime.fused_sample(solver, model, plan, xt, prior, cond_vec, w_cfg, feed)
+    return _sample_unguided(solver, model, plan, xt, prior, cond_vec, w_cfg, feed, unet_only=True)
 
 
 def _scoped(fn):

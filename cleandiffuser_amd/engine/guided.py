@@ -71,7 +71,7 @@ def guided_sample(solver, model, plan, xt, prior, cond_vec, w_cfg, w_cg, feed) -
         from . import bigbatch
         if not runtime._is_janner(net) or use_cond:
             return None
-        gemm_bound = bigbatch._bound(net, ("chiunet", h), lambda: bigbatch._bind_janner_gemm(net, h, xt.device))
+        gemm_bound = bigbatch.unet_binding(net, h, xt.device)
         if gemm_bound is None or d != gemm_bound.struct.act_dim:
             return None
     if runtime._is_chiunet(net) and not use_cond:
@@ -136,7 +136,7 @@ def guided_sample(solver, model, plan, xt, prior, cond_vec, w_cfg, w_cg, feed) -
             den_ptr = ctypes.POINTER(CdxUnet2Launch)()               # NULL: the denoiser is the GEMM executor
             gemm_kw = dict(denoiser_gemm=ctypes.cast(ctypes.pointer(gemm_bound.struct), ctypes.c_void_p),
                            denoiser_emb_dim=gemm_bound.struct.emb_dim,
-                           denoiser_chunk=bigbatch.CHUNK_OVERRIDE["chiunet"] or bigbatch._chiunet_chunk(b, h, getattr(net, "model_dim", 32), 1))
+                           denoiser_chunk=bigbatch.unet_chunk(net, b, h))
         else:
             den = runtime2.describe_forward(den_comp, batch=b, emb=den_emb, t_per_wg=den_t,
                                             emb_per_traj=use_cond or runtime._is_chiunet(net))

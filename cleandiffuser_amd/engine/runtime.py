@@ -306,13 +306,10 @@ def device_times(plan, device) -> torch.Tensor:
     return cached(plan, ("t", str(device)), lambda: torch.tensor([st.t for st in plan.steps], dtype=dt, device=device))
 
 
-def steps_to_device(plan, device) -> torch.Tensor:
-    from .plan import cached
-    return cached(plan, ("steps", str(device)), lambda: _pack_steps(plan, device))
-
-
-def _pack_steps(plan, device) -> torch.Tensor:
-    arr = (CdxStep * len(plan.steps))()
+def pack_steps(plan):
+    """plan.Step list -> cdx_step array on the host; noise_idx numbers the stochastic steps.  At least one record long: callers
+    hand its address to C also for an empty plan."""
+    arr = (CdxStep * max(len(plan.steps), 1))()
     k = 0
     for i, st in enumerate(plan.steps):
         arr[i].kind, arr[i].vsel, arr[i].push, arr[i].flags = st.kind, st.vsel, int(st.push), int(st.flags)
@@ -323,8 +320,23 @@ def _pack_steps(plan, device) -> torch.Tensor:
             arr[i].noise_idx, k = k, k + 1
         else:
             arr[i].noise_idx = -1
-    raw = np.frombuffer(bytes(arr), dtype=np.uint8).copy()
-    return torch.from_numpy(raw).to(device)
+    return arr
+
+
+def host_steps(plan):
+    """The host-resident step records (the C loops of the big-batch and guided executors read them while enqueuing); memoised on the plan."""
+    from .plan import cached
+    return cached(plan, ("host_steps",), lambda: pack_steps(plan))
+
+
+def steps_to_device(plan, device) -> torch.Tensor:
+    """The same records as device bytes for the program kernel: exactly len(plan.steps) of them; memoised on the plan."""
+    from .plan import cached
+
+    def upload():
+        raw = bytes(host_steps(plan))[:len(plan.steps) * ctypes.sizeof(CdxStep)]
+        return torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy()).to(device)
+    return cached(plan, ("steps", str(device)), upload)
 
 
 def mlp_tile(batch: int) -> int:
