@@ -197,6 +197,68 @@ def _records(w_eff: torch.Tensor, mode: int) -> Tuple[torch.Tensor, int]:
     return wp.reshape(n_ct, taps * cc, 64, 4).contiguous(), cc
 
 
+def _source_records(w: torch.Tensor, srcs: List["Act"], mode: int) -> List[Tuple[torch.Tensor, int]]:
+    """`_records` of a conv over the channel concat of `srcs`, cut at the boundaries between the sources: one (records, chunks per
+    tap) per source -- a K slice never straddles the sources (the item record names the one slot it reads)."""
+    los = [sum(a.chans for a in srcs[:i]) for i in range(len(srcs))]
+    return [_records(w[:, :, lo:lo + a.chans], mode) for a, lo in zip(srcs, los)]
+
+
+def _slice_edges(n: int, k: int, ring: int) -> List[int]:
+    """The k + 1 edges that cut `n` records into `k` K slices: even cuts, moved to the nearest multiple of the ring depth when every
+    slice keeps at least two ring revolutions -- only ring-aligned slices take the kernel's immediate-offset loop (round 5: op 24G's
+    13 / 13 / 14 cut ran the general loop at 310 cycles per record)."""
+    al = ring if n >= 2 * ring * k else 1
+    return [min(n, (j * n // k + al // 2) // al * al) for j in range(k)] + [n]
+
+
+def _deal_over_simds(items: list, item_src: List[int], nw: int):
+    """Waves w and w + 4 share a SIMD: deal the items so that the SIMDs' record totals come out level (largest first onto the least
+    loaded SIMD with a free wave).  An item carries its own tile and partial-sum slot: the order changes no result."""
+    load, free, place = [0] * 4, [[sm, sm + 4] for sm in range(4)], {}
+    for idx in sorted(range(nw), key=lambda t: -items[t][I2_NQ]):
+        sm = min((q for q in range(4) if free[q]), key=lambda q: load[q])
+        place[free[sm].pop(0)] = idx
+        load[sm] += items[idx][I2_NQ]
+    return [items[place[w]] for w in range(nw)], [item_src[place[w]] for w in range(nw)]
+
+
+@dataclass
+class _Stream:
+    """One record stream of a single-phase op: the weights of one conv over one source slot."""
+    src: int                          # index of the slot it reads in the op's source list
+    recs: torch.Tensor                # [row tile][record][64][4]
+    ccn: int                          # chunks per tap
+    pad: int
+    post: bool                        # summed AFTER the norm / activation of the main conv (a 1x1 skip conv)
+
+
+@dataclass
+class _ConvView:
+    """A conv op as this builder's member sees it: what `_geometry`, `_tile_shape` and `_member_view` decide."""
+    c_out: int
+    l_out: int
+    phases: list                      # (taps-in-row-order weights, item pad, output offset) per phase
+    l_cols: int                       # columns the tiles cover (k x l_out for a grouped op)
+    mode: int
+    rows: int
+    cols: int
+    nt: int
+    n_rt: int
+    n_cg: int
+    my_rts: List[int]                 # row tiles this member computes
+    gop: bool = False                 # a GROUPED op: 1/k of the channels for all k trajectories of the group
+    xg: int = 0                       # W2_XG
+
+    def __post_init__(self):
+        self.coutp = pad32(self.c_out)
+        self.tiles = len(self.my_rts) * self.n_cg * len(self.phases)
+        # staged partial tiles: [K slice][output position][channel]; a grouped op stages only the member's channels, for k x l_out columns
+        self.sstride = (len(self.my_rts) * self.rows + 4) if self.gop else self.coutp + 4
+        self.l_stage = self.l_cols if self.gop else self.l_out
+        self.rt0 = self.my_rts[0] if self.gop else 0
+
+
 class _Builder2:
     def __init__(self, device, nw: int = NW2):
         if nw not in (NW2, NW2_MAX):
@@ -287,11 +349,42 @@ class _Builder2:
 
         `transposed`: ConvTranspose1d(k=4, stride=2, pad=1) as two 2-tap convs, one per output parity.  `phases`: explicit list of
         (taps-in-row-order weights [C_out][taps][C_in], item pad, output offset) of a stride-2 scatter (the backward of a strided
-        conv); phases may have different tap counts."""
-        c_out, taps, c_in = w_eff.shape
-        l_out = dst.length
+        conv); phases may have different tap counts.
+
+        Returns False, with nothing emitted (no blob chunk, MAC, op or staging area), when the `extra` convs would cost the main conv
+        more than an op of their own (`fuse_max`).  Blob order of an op: record streams, bias, post-bias, gamma, beta."""
+        c_out, _, c_in = w_eff.shape
         assert c_in == sum(a.chans for a in srcs) and dst.chans == c_out and 1 <= len(srcs) <= 2
-        gop = False
+        extra = list(extra or [])
+        groupable = phases is None and not transposed and stride == 1 and not col_norm
+        phases, l_cols, cstride, ostride = self._geometry(srcs, dst.length, w_eff, stride, pad, transposed, phases)
+        v = self._member_view(srcs, dst, w_eff, extra, res, phases, l_cols, groupable=groupable, cuttable=bwd is None and save is None)
+        if len(phases) == 1:
+            plan = self._plan_single_phase(v, srcs, extra, stride)
+            if plan is None:
+                return False
+        else:
+            assert not extra, "extra convs ride on single-phase ops only"
+            plan = self._plan_phases(v, srcs)
+        items, item_src, ksplit, kpost, pbias, all_srcs = plan
+        words = {W2_KIND: KIND2_CONV, W2_COUT: c_out, W2_LOUT: v.l_out, W2_LCOLS: v.l_cols, W2_CSTRIDE: cstride, W2_OSTRIDE: ostride,
+                 W2_MODE: v.mode, W2_NT: v.nt, W2_NITEMS: len(items), W2_DST_STRIDE: dst.stride, W2_SSTRIDE: v.sstride,
+                 W2_KSPLIT: ksplit, W2_COUTP: v.coutp, W2_KPOST: kpost, W2_XG: v.xg}
+        if v.gop:
+            words[W2_GMAP] = (v.l_out.bit_length() - 1) | ((v.l_out + 2 * HALO2) << 8)
+        reads, writes = self._epilogue_words(words, v, dst, all_srcs, bias, pbias, gn=gn, bwd=bwd, save=save, emb_off=emb_off, film=film, res=res,
+                                             pred=pred, bias_row=bias_row, act=act, col_norm=col_norm, cg_real=cg_real, out_div=out_div)
+        self._emit(words, dict(srcs=list(all_srcs), res=res, dst=dst, save=(save[0] if save is not None else (bwd["save"] if bwd else None)),
+                               dst2=(bwd.get("dst2") if bwd else None), reads=reads, writes=writes, gop=v.gop), items, item_src)
+        self.stage = max(self.stage, (ksplit + kpost) * v.l_stage * v.sstride)
+        self.macs += sum(c_out * (l_cols if len(phases) > 1 else v.l_out) * w.shape[1] * c_in for w, _, _ in phases)
+        return True
+
+    def _geometry(self, srcs: List[Act], l_out: int, w_eff: torch.Tensor, stride: int, pad: int, transposed: bool, phases):
+        """(phases, l_cols, cstride, ostride): `phases` = (taps-in-row-order weights, item pad, output offset) per record stream of a row
+        tile, `l_cols` the columns the tiles cover, input rows and output rows per column.  A plain conv is one phase over its l_out
+        positions; a stride-2 scatter (explicit `phases`, or `transposed`) one phase per output parity over the SOURCE's positions."""
+        taps = w_eff.shape[1]
         if phases is not None:
             if l_out != 2 * srcs[0].length or len(srcs) != 1:
                 raise ValueError("explicit phases describe a stride-2 scatter of one source")
@@ -307,237 +400,216 @@ class _Builder2:
                 raise ValueError(f"kernel size {taps} needs more than {HALO2} halo rows")
             phases = [(w_eff, pad, 0)]
             l_cols, cstride, ostride = l_out, stride, 1
-            # ---- grouped op (member view of a grouped program): all k trajectories of the group ride the column axis ----
-            ex_srcs = [a for ex in (extra or []) for a in ex["srcs"]]
-            w_bytes = 4 * (w_eff.numel() + sum(ex["w_eff"].numel() for ex in (extra or [])))
-            gop = (self.grouped and self.group_on and self.member[1] > 1 and stride == 1 and bwd is None and save is None and not col_norm
-                   and dst.gcap and all(a.gcap and a.length == l_out for a in list(srcs) + ex_srcs) and (res is None or res.gcap)
-                   and w_bytes >= group_min_bytes())
-            if gop:
-                l_cols = self.member[1] * l_out
-        if len(phases) != 1 or transposed:
-            gop = False
         for w, ppad, _ in phases:
             if ppad > HALO2 or (w.shape[1] - 1 - ppad) > HALO2:
                 raise ValueError("phase reaches past the halo rows")
+        return phases, l_cols, cstride, ostride
+
+    def _tile_shape(self, l_cols: int, c_out: int):
+        """(mode, rows, cols, nt, n_rt, n_cg): the MFMA block shape of a conv over `l_cols` columns, the rows x cols one block covers,
+        the blocks a 4x4 tile puts side by side, and the row tiles x column groups that cover the output.  Short, wide layers
+        (<= 8 columns, C_out a multiple of 64) take 64 x 4 blocks -- no half-empty 16-column MFMAs."""
         mode = MODE_4X4 if (l_cols <= 8 and c_out % 64 == 0 and self.allow_4x4) else MODE_16X16
         rows, cols = (16, 16) if mode == MODE_16X16 else (64, 4)
         nt = 2 if (mode == MODE_4X4 and l_cols > 4) else 1
-        n_rt = -(-c_out // rows)
-        n_cg = -(-l_cols // (nt * cols))
-        coutp = pad32(c_out)
-        # ---- member view of a split program: which row tiles are this member's, and which lane groups of the epilogue that is ----
+        return mode, rows, cols, nt, -(-c_out // rows), -(-l_cols // (nt * cols))
+
+    def _member_view(self, srcs: List[Act], dst: Act, w_eff: torch.Tensor, extra: List[dict], res: Optional[Act], phases, l_cols: int, *,
+                     groupable: bool, cuttable: bool) -> _ConvView:
+        """Which of the op's row tiles this builder's member computes: a GROUPED op, a SPLIT op or the whole op.
+
+        Grouped op (member view of a grouped program; `groupable`: a plain stride-1 conv without a per-position norm): all k
+        trajectories of the group ride the column axis, the member computes 1/k of the row tiles.  Taken only if every slot the op
+        touches can hold the group's trajectories side by side (`gcap`), the op streams at least `group_min_bytes()` of weights, and
+        the member's 1/k of the row tiles = whole GroupNorm lane groups with at most two float4 items per epilogue lane (the grouped
+        epilogue of the kernel is instantiated for 1 and 2) -- or the op stays an ordinary one on the member's own trajectory.
+        Split op (member view of a split program): 1/k of the row tiles, whole lane groups again, if a wave of the uncut op streams
+        at least SPLIT_MIN_RECORDS records.  Both record the tile the members exchange (`xchg_floats`); `cuttable`: no backward op."""
+        c_out, l_out = dst.chans, dst.length
         mem, ksp = self.member
+        coutp, cgw = pad32(c_out), pad32(c_out) // GROUPS2
+        ex_srcs = [a for ex in extra for a in ex["srcs"]]
+        w_bytes = 4 * (w_eff.numel() + sum(ex["w_eff"].numel() for ex in extra))
+        gop = (groupable and self.grouped and self.group_on and ksp > 1 and cuttable
+               and dst.gcap and all(a.gcap and a.length == l_out for a in list(srcs) + ex_srcs) and (res is None or res.gcap)
+               and w_bytes >= group_min_bytes())
+        if gop:
+            _, rows, _, _, n_rt, n_cg = shape = self._tile_shape(ksp * l_out, c_out)
+            lo_c, hi_c = mem * n_rt // ksp * rows, (mem + 1) * n_rt // ksp * rows
+            if not (n_rt % ksp or n_cg != 1 or coutp != c_out or lo_c % cgw or hi_c % cgw or GROUPS2 % ksp or -(-(cgw // 4 * l_out) // 32) > 2):
+                self.xchg_floats = max(self.xchg_floats, ksp * l_out * coutp)
+                for a in list(srcs) + ex_srcs + [dst] + ([res] if res is not None else []):
+                    a.gk = ksp                               # these slots hold the group's k trajectories from now on
+                return _ConvView(c_out, l_out, phases, ksp * l_out, *shape, list(range(mem * n_rt // ksp, (mem + 1) * n_rt // ksp)),
+                                 gop=True, xg=(lo_c // cgw) | ((hi_c // cgw) << 8) | XG_XCHG | XG_GOP)
+        mode, rows, _, _, n_rt, n_cg = shape = self._tile_shape(l_cols, c_out)
         my_rts, xg = list(range(n_rt)), 0
         k_chunks = sum(-(-a.chans // (16 if mode == MODE_16X16 else 4)) for a in srcs) * phases[0][0].shape[1]     # records per row tile
         worth = k_chunks * n_rt * n_cg / self.nw >= SPLIT_MIN_RECORDS
-        if gop:
-            # the member's 1/k of the row tiles = whole GroupNorm lane groups, or the op stays an ordinary one on the member's own trajectory
-            cgw = coutp // GROUPS2
-            lo_c, hi_c = mem * n_rt // ksp * rows, (mem + 1) * n_rt // ksp * rows
-            # (... and at most two float4 items per epilogue lane: the grouped epilogue of the kernel is instantiated for 1 and 2)
-            if n_rt % ksp or n_cg != 1 or coutp != c_out or lo_c % cgw or hi_c % cgw or GROUPS2 % ksp or -(-(cgw // 4 * l_out) // 32) > 2:
-                gop, l_cols = False, l_out
-                mode = MODE_4X4 if (l_cols <= 8 and c_out % 64 == 0 and self.allow_4x4) else MODE_16X16
-                rows, cols = (16, 16) if mode == MODE_16X16 else (64, 4)
-                nt = 2 if (mode == MODE_4X4 and l_cols > 4) else 1
-                n_rt, n_cg = -(-c_out // rows), -(-l_cols // (nt * cols))
-                my_rts = list(range(n_rt))
-            else:
-                my_rts = list(range(mem * n_rt // ksp, (mem + 1) * n_rt // ksp))
-                xg = (lo_c // cgw) | ((hi_c // cgw) << 8) | XG_XCHG | XG_GOP
-                self.xchg_floats = max(self.xchg_floats, l_cols * coutp)
-                for a in list(srcs) + ex_srcs + [dst] + ([res] if res is not None else []):
-                    a.gk = ksp                               # these slots hold the group's k trajectories from now on
-        elif ksp > 1 and not self.grouped and self.group_on and worth and len(phases) == 1 and n_rt > 1 and bwd is None and save is None and (n_rt % ksp == 0 or ksp % n_rt == 0):
+        if (ksp > 1 and not self.grouped and self.group_on and worth and len(phases) == 1 and n_rt > 1 and cuttable
+                and (n_rt % ksp == 0 or ksp % n_rt == 0)):
             cand = list(range(mem * n_rt // ksp, (mem + 1) * n_rt // ksp)) if n_rt >= ksp else [mem * n_rt // ksp]
-            cgw = coutp // GROUPS2
             lo_c, hi_c = cand[0] * rows, (cand[-1] + 1) * rows
             if lo_c % cgw == 0 and hi_c % cgw == 0:             # whole GroupNorm lane groups
                 my_rts, xg = cand, (lo_c // cgw) | (min(hi_c // cgw, GROUPS2) << 8) | (1 << 16)
                 self.xchg_floats = max(self.xchg_floats, l_out * coutp)
-        tiles = len(my_rts) * n_cg * len(phases)
-        # staged partial tiles: [K slice][output position][channel]; a grouped op stages only the member's channels, for k x l_out columns
-        sstride = (len(my_rts) * rows + 4) if gop else coutp + 4
-        l_stage = l_cols if gop else l_out
-        rt0 = my_rts[0] if gop else 0
-        nw, ring = self.nw, ring_depth(self.nw)
-        # record stream of a (phase, row tile): [source 0: taps x chunks | source 1: taps x chunks]; a K slice never straddles the
-        # sources.  K slices: every source's record range is cut evenly; with two sources (a concat) each source gets at least one
-        # slice and the epilogue sums the staged partials.  Phases with fewer taps get the same NUMBER of slices (shorter ones).
-        extra = list(extra or [])
-        all_srcs = list(srcs)
-        kpost, pbias = 0, None
-        if len(phases) == 1:
-            # ---- single phase: a list of record STREAMS (one per source of the main conv and of every extra conv); every stream is
-            # cut into K slices, one work item per (slice, tile).  Slice budget = waves per tile, handed out greedily to the stream with
-            # the most records per slice (>= 1 per stream, >= MIN_SLICE records per slice, staging area <= max_stage).
-            streams = []                                     # dict(act index, records, ccn, pad, post)
-            lo = 0
-            for a in srcs:
-                r, ccn = _records(phases[0][0][:, :, lo:lo + a.chans], mode)
-                streams.append(dict(src=all_srcs.index(a), recs=r, ccn=ccn, pad=phases[0][1], post=False))
-                lo += a.chans
-            for ex in extra:
-                w2, lo = ex["w_eff"], 0
-                assert w2.shape[0] == c_out and w2.shape[2] == sum(a.chans for a in ex["srcs"]) and stride == 1
-                if ex["pad"] > HALO2 or (w2.shape[1] - 1 - ex["pad"]) > HALO2:
-                    raise ValueError("extra conv reaches past the halo rows")
-                for a in ex["srcs"]:
-                    if a not in all_srcs:
-                        all_srcs.append(a)
-                    r, ccn = _records(w2[:, :, lo:lo + a.chans], mode)
-                    streams.append(dict(src=all_srcs.index(a), recs=r, ccn=ccn, pad=ex["pad"], post=bool(ex.get("post"))))
-                    lo += a.chans
-                if ex.get("post"):
-                    pb = ex.get("bias")
-                    pbias = (pbias if pbias is not None else torch.zeros(c_out, device=self.device)) + \
-                        (pb.detach().to(self.device) if pb is not None else 0)
-                else:
-                    assert ex.get("bias") is None, "bias of a summed extra conv: fold it into the main bias"
-            budget = max(len(streams), nw // tiles if tiles < nw else 1)
-            if gop:      # the post-norm extra streams (1x1 skip) ride as second-round items: the main conv keeps every wave
-                budget = (nw // tiles if tiles < nw else 1) + sum(1 for st in streams if st["post"])
-                if os.environ.get("CDX_DBG_LONE") == "1":       # (diagnostic: one K slice per tile -- four waves run the steady loop alone on their SIMDs)
-                    budget = 1 + sum(1 for st in streams if st["post"])
-            per = [1] * len(streams)
-            n_of = [st["recs"].shape[1] for st in streams]
-            single_round = False
-            uneven = {}                                      # stream -> explicit slice ends (see the grouped ops with a skip conv below)
-            kpost_streams = [i for i in range(len(streams)) if streams[i]["post"]]
+        return _ConvView(c_out, l_out, phases, l_cols, *shape, my_rts, xg=xg)
 
-            def grow():
-                cand = [i for i in range(len(streams)) if n_of[i] // (per[i] + 1) >= MIN_SLICE]
-                return max(cand, key=lambda i: n_of[i] / per[i]) if cand else None
-            while sum(per) < budget and (sum(per) + 1) * l_stage * sstride <= self.max_stage:
-                i = grow()
-                if i is None:
-                    break
-                per[i] += 1
-            if extra and max(n_of[i] / per[i] for i in range(len(srcs))) > self.fuse_max:
-                # the main conv is a long, stream-bound K loop: giving waves away to the extra conv costs it more than an op of its own
-                return False
-            self.macs += sum(c_out * l_out * ex["w_eff"].shape[1] * ex["w_eff"].shape[2] for ex in extra)
-            if gop and kpost_streams:
-                # A grouped op whose block carries a 1x1 skip conv: its second-round items (the skip streams) start with an empty ring
-                # (~1.3 k cycles until their first MFMA) on the waves that also hold a first-round slice.  Cut the main conv so that
-                # (i) every slice is a multiple of the ring -- only such slices take the kernel's immediate-offset loop (round 5:
-                # op 24G's 13 / 13 / 14 cut ran the general loop at 310 cycles per record) -- and (ii) the slices of the waves that get
-                # a second-round item are one ring revolution shorter than the others' (r05 op profile: ops 16G / 24G waited ~3.6 k
-                # cycles at their staging barrier for the four waves that drew 48 records instead of 40).
-                n_first = nw // tiles if tiles < nw else 1
-                main = [i for i in range(len(streams)) if not streams[i]["post"]]
-                uneven_on = os.environ.get("CDX_UNET2_UNEVEN_CUT", "1") != "0"
-                if uneven_on and len(main) == 1 and n_first - len(kpost_streams) >= 2 and n_of[main[0]] >= 2 * ring * (n_first - len(kpost_streams)):
-                    # enough waves per tile for the skip streams to be FIRST-round items next to ring-aligned main slices: one round, no
-                    # empty-ring start at all (24G: 24 / 16 main + 16 / 8 skip records per tile instead of 13 / 13 / 14 + a second round)
-                    per = [1] * len(streams)
-                    per[main[0]] = n_first - len(kpost_streams)
-                    single_round = True
-                elif uneven_on and len(main) == 1 and n_first == 2 and n_of[main[0]] >= 4 * ring and n_of[main[0]] % (2 * ring) == 0:
-                    per[main[0]] = 2
-                    uneven[main[0]] = [n_of[main[0]] // 2 - ring, n_of[main[0]]]
-                    spare = budget - 2 - sum(per[i] for i in range(len(streams)) if streams[i]["post"])
-                    for i in sorted((i for i in range(len(streams)) if streams[i]["post"]), key=lambda i: -n_of[i]):
-                        while spare < 0 and per[i] > 1:
-                            per[i] -= 1
-                            spare += 1
-            order = [i for i in range(len(streams)) if not streams[i]["post"]] + [i for i in range(len(streams)) if streams[i]["post"]]
-            kpost = sum(per[i] for i in range(len(streams)) if streams[i]["post"])
-            ksplit = sum(per) - kpost                        # slices summed BEFORE the norm; the post slices follow them in the stage
-            items, item_src, ks = [], [], 0
-            for i in order:
-                st, n, k = streams[i], n_of[i], per[i]
-                woff = self.add(st["recs"].contiguous())
-                al = ring if n >= 2 * ring * k else 1
-                edge = [min(n, (j * n // k + al // 2) // al * al) for j in range(k)] + [n]
-                if i in uneven:
-                    edge = [0] + uneven[i]
-                for j in range(k):
-                    q0, q1 = edge[j], edge[j + 1]
-                    for tile in range(n_rt * n_cg):
-                        rt, cgi = tile % n_rt, tile // n_rt
-                        if rt not in my_rts:
-                            continue
-                        items.append([woff + (rt * n + q0) * 256, q1 - q0, (q0 // st["ccn"]) | ((q0 % st["ccn"]) << 8),
-                                      ks * l_stage * sstride + (rt - rt0) * rows, cgi * nt * cols, st["pad"] | (0 << 8), 0, st["ccn"]])
-                        item_src.append(st["src"])
-                    ks += 1
-            stage_slices = ksplit + kpost
-            if single_round and len(items) == nw:
-                # waves w and w + 4 share a SIMD: deal the items so that the SIMDs' record totals come out level (largest first onto the
-                # least loaded SIMD with a free wave).  An item carries its own tile and partial-sum slot: the order changes no result.
-                load, free, place = [0] * 4, [[sm, sm + 4] for sm in range(4)], {}
-                for idx in sorted(range(nw), key=lambda t: -items[t][I2_NQ]):
-                    sm = min((q for q in range(4) if free[q]), key=lambda q: load[q])
-                    place[free[sm].pop(0)] = idx
-                    load[sm] += items[idx][I2_NQ]
-                items = [items[place[w]] for w in range(nw)]
-                item_src = [item_src[place[w]] for w in range(nw)]
-        else:
-            assert not extra, "extra convs ride on single-phase ops only"
-            # record stream of a (phase, row tile): [source 0: taps x chunks | source 1: taps x chunks]; a K slice never straddles the
-            # sources.  Phases with fewer taps get the same NUMBER of slices (shorter ones).
-            per_src = max(1, (nw // tiles if tiles < nw else 1) // len(srcs))
-            ph_segs = []
-            for w, _, _ in phases:
-                segs, lo = [], 0
-                for a in srcs:
-                    segs.append(_records(w[:, :, lo:lo + a.chans], mode))
-                    lo += a.chans
-                ph_segs.append(segs)
-            per = [min([per_src] + [max(1, segs[si][0].shape[1] // MIN_SLICE) for segs in ph_segs]) for si in range(len(srcs))]
-            while sum(per) > len(srcs) and sum(per) * l_out * sstride > self.max_stage:
-                per[per.index(max(per))] -= 1
-            ph_info = []
-            for (w, ppad, ooff), segs in zip(phases, ph_segs):
-                seg_n = [r.shape[1] for r, _ in segs]
-                cuts, base = [], 0                          # (first record, one past the last, source index, source base) per slice
-                for si, (n, k) in enumerate(zip(seg_n, per)):
-                    al = ring if n >= 2 * ring * k else 1
-                    edge = [min(n, (j * n // k + al // 2) // al * al) for j in range(k)] + [n]
-                    cuts += [(base + edge[j], base + edge[j + 1], si, base) for j in range(k)]
-                    base += n
-                woff = self.add(torch.cat([r for r, _ in segs], dim=1).contiguous())
-                ph_info.append(dict(segs=segs, nqt=sum(seg_n), cuts=cuts, woff=woff, pad=ppad, ooff=ooff))
-            ksplit = max(len(pi["cuts"]) for pi in ph_info)
-            items, item_src = [], []
-            for ks in range(ksplit):
-                for tile in range(n_rt * n_cg):
-                    rt, cgi = tile % n_rt, tile // n_rt
-                    for pi in ph_info:
-                        q0, q1, si, sbase = pi["cuts"][ks]
-                        ccn = pi["segs"][si][1]
-                        items.append([pi["woff"] + (rt * pi["nqt"] + q0) * 256, q1 - q0, ((q0 - sbase) // ccn) | (((q0 - sbase) % ccn) << 8),
-                                      ks * l_out * sstride + rt * rows, cgi * nt * cols, pi["pad"] | (pi["ooff"] << 8), 0, ccn])
-                        item_src.append(si)
-            if any(len(pi["cuts"]) != ksplit for pi in ph_info):
-                raise ValueError("phases with different K-slice counts are not supported (stale partial tiles)")
-            stage_slices = ksplit
-        words = {W2_KIND: KIND2_CONV, W2_COUT: c_out, W2_LOUT: l_out, W2_LCOLS: l_cols, W2_CSTRIDE: cstride, W2_OSTRIDE: ostride,
-                 W2_MODE: mode, W2_NT: nt, W2_NITEMS: len(items), W2_DST_STRIDE: dst.stride, W2_SSTRIDE: sstride,
-                 W2_KSPLIT: ksplit, W2_COUTP: coutp, W2_KPOST: kpost}
+    def _slice_counts(self, v: _ConvView, streams: List[_Stream], n_main: int, fusing: bool):
+        """K slices per stream of a single-phase op -> (per, uneven, single_round), or None: the fuse is refused.  Slice budget = waves
+        per tile, handed out greedily to the stream with the most records per slice (>= 1 per stream, >= MIN_SLICE records per slice,
+        staging area <= max_stage).  `fusing` (the op carries extra convs): a main conv -- the first `n_main` streams -- left with K
+        slices longer than `fuse_max` is a long, stream-bound K loop: giving waves away to the extra conv costs it more than an op of its own.
+
+        A grouped op whose block carries a 1x1 skip conv: its second-round items (the skip streams) start with an empty ring
+        (~1.3 k cycles until their first MFMA) on the waves that also hold a first-round slice.  Cut the main conv so that
+        (i) every slice is a multiple of the ring -- only such slices take the kernel's immediate-offset loop (round 5:
+        op 24G's 13 / 13 / 14 cut ran the general loop at 310 cycles per record) -- and (ii) the slices of the waves that get
+        a second-round item are one ring revolution shorter than the others' (r05 op profile: ops 16G / 24G waited ~3.6 k
+        cycles at their staging barrier for the four waves that drew 48 records instead of 40): `uneven` = stream -> slice ends.
+        `single_round`: enough waves per tile for the skip streams to be FIRST-round items next to ring-aligned main slices: one round, no
+        empty-ring start at all (24G: 24 / 16 main + 16 / 8 skip records per tile instead of 13 / 13 / 14 + a second round)."""
+        nw, ring = self.nw, ring_depth(self.nw)
+        n_first = nw // v.tiles if v.tiles < nw else 1
+        post = [i for i, st in enumerate(streams) if st.post]
+        budget = max(len(streams), n_first)
+        if v.gop:      # the post-norm extra streams (1x1 skip) ride as second-round items: the main conv keeps every wave
+            budget = n_first + len(post)
+            if os.environ.get("CDX_DBG_LONE") == "1":       # (diagnostic: one K slice per tile -- four waves run the steady loop alone on their SIMDs)
+                budget = 1 + len(post)
+        per = [1] * len(streams)
+        n_of = [st.recs.shape[1] for st in streams]
+        while sum(per) < budget and (sum(per) + 1) * v.l_stage * v.sstride <= self.max_stage:
+            cand = [i for i in range(len(streams)) if n_of[i] // (per[i] + 1) >= MIN_SLICE]
+            if not cand:
+                break
+            per[max(cand, key=lambda i: n_of[i] / per[i])] += 1
+        if fusing and max(n_of[i] / per[i] for i in range(n_main)) > self.fuse_max:
+            return None
+        single_round, uneven = False, {}
+        if v.gop and post:
+            main = [i for i, st in enumerate(streams) if not st.post]
+            uneven_on = os.environ.get("CDX_UNET2_UNEVEN_CUT", "1") != "0"
+            if uneven_on and len(main) == 1 and n_first - len(post) >= 2 and n_of[main[0]] >= 2 * ring * (n_first - len(post)):
+                per = [1] * len(streams)
+                per[main[0]] = n_first - len(post)
+                single_round = True
+            elif uneven_on and len(main) == 1 and n_first == 2 and n_of[main[0]] >= 4 * ring and n_of[main[0]] % (2 * ring) == 0:
+                per[main[0]] = 2
+                uneven[main[0]] = [n_of[main[0]] // 2 - ring, n_of[main[0]]]
+                spare = budget - 2 - sum(per[i] for i in post)
+                for i in sorted(post, key=lambda i: -n_of[i]):
+                    while spare < 0 and per[i] > 1:
+                        per[i] -= 1
+                        spare += 1
+        return per, uneven, single_round
+
+    def _plan_single_phase(self, v: _ConvView, srcs: List[Act], extra: List[dict], stride: int):
+        """Work items of a single-phase op -> (items, item sources, ksplit, kpost, post-bias, slots read), or None (nothing added
+        anywhere): the fuse is refused.  A list of record STREAMS (one per source of the main conv and of every extra conv); every
+        stream is cut into K slices (`_slice_counts`), one work item per (slice, tile of this member).  The streams join the blob main
+        streams first, then the post-norm ones, whose slices follow the main ones in the staging area."""
+        w, ppad, _ = v.phases[0]
+        all_srcs, pbias = list(srcs), None
+        streams = [_Stream(all_srcs.index(a), r, ccn, ppad, False) for a, (r, ccn) in zip(srcs, _source_records(w, srcs, v.mode))]
+        for ex in extra:
+            w2 = ex["w_eff"]
+            assert w2.shape[0] == v.c_out and w2.shape[2] == sum(a.chans for a in ex["srcs"]) and stride == 1
+            if ex["pad"] > HALO2 or (w2.shape[1] - 1 - ex["pad"]) > HALO2:
+                raise ValueError("extra conv reaches past the halo rows")
+            for a, (r, ccn) in zip(ex["srcs"], _source_records(w2, ex["srcs"], v.mode)):
+                if a not in all_srcs:
+                    all_srcs.append(a)
+                streams.append(_Stream(all_srcs.index(a), r, ccn, ex["pad"], bool(ex.get("post"))))
+            if ex.get("post"):
+                pb = ex.get("bias")
+                pbias = (pbias if pbias is not None else torch.zeros(v.c_out, device=self.device)) + \
+                    (pb.detach().to(self.device) if pb is not None else 0)
+            else:
+                assert ex.get("bias") is None, "bias of a summed extra conv: fold it into the main bias"
+        counts = self._slice_counts(v, streams, len(srcs), bool(extra))
+        if counts is None:
+            return None
+        per, uneven, single_round = counts
+        self.macs += sum(v.c_out * v.l_out * ex["w_eff"].shape[1] * ex["w_eff"].shape[2] for ex in extra)
+        order = [i for i, st in enumerate(streams) if not st.post] + [i for i, st in enumerate(streams) if st.post]
+        kpost = sum(per[i] for i, st in enumerate(streams) if st.post)
+        ksplit = sum(per) - kpost                        # slices summed BEFORE the norm; the post slices follow them in the stage
+        items, item_src, ks = [], [], 0
+        for i in order:
+            st, n, k = streams[i], streams[i].recs.shape[1], per[i]
+            woff = self.add(st.recs.contiguous())
+            edge = [0] + uneven[i] if i in uneven else _slice_edges(n, k, ring_depth(self.nw))
+            for j in range(k):
+                q0, q1 = edge[j], edge[j + 1]
+                for tile in range(v.n_rt * v.n_cg):
+                    rt, cgi = tile % v.n_rt, tile // v.n_rt
+                    if rt not in v.my_rts:
+                        continue
+                    items.append([woff + (rt * n + q0) * 256, q1 - q0, (q0 // st.ccn) | ((q0 % st.ccn) << 8),
+                                  ks * v.l_stage * v.sstride + (rt - v.rt0) * v.rows, cgi * v.nt * v.cols, st.pad | (0 << 8), 0, st.ccn])
+                    item_src.append(st.src)
+                ks += 1
+        if single_round and len(items) == self.nw:
+            items, item_src = _deal_over_simds(items, item_src, self.nw)
+        return items, item_src, ksplit, kpost, pbias, all_srcs
+
+    def _plan_phases(self, v: _ConvView, srcs: List[Act]):
+        """Work items of a multi-phase op (a stride-2 scatter), as `_plan_single_phase` returns them.  Record stream of a (phase, row
+        tile): [source 0: taps x chunks | source 1: taps x chunks]; a K slice never straddles the sources.  K slices: every source's
+        record range is cut evenly; with two sources (a concat) each source gets at least one slice and the epilogue sums the staged
+        partials.  Phases with fewer taps get the same NUMBER of slices (shorter ones)."""
+        nw, ring = self.nw, ring_depth(self.nw)
+        per_src = max(1, (nw // v.tiles if v.tiles < nw else 1) // len(srcs))
+        ph_segs = [_source_records(w, srcs, v.mode) for w, _, _ in v.phases]
+        per = [min([per_src] + [max(1, segs[si][0].shape[1] // MIN_SLICE) for segs in ph_segs]) for si in range(len(srcs))]
+        while sum(per) > len(srcs) and sum(per) * v.l_out * v.sstride > self.max_stage:
+            per[per.index(max(per))] -= 1
+        ph_info = []
+        for (w, ppad, ooff), segs in zip(v.phases, ph_segs):
+            seg_n = [r.shape[1] for r, _ in segs]
+            cuts, base = [], 0                          # (first record, one past the last, source index, source base) per slice
+            for si, (n, k) in enumerate(zip(seg_n, per)):
+                edge = _slice_edges(n, k, ring)
+                cuts += [(base + edge[j], base + edge[j + 1], si, base) for j in range(k)]
+                base += n
+            woff = self.add(torch.cat([r for r, _ in segs], dim=1).contiguous())
+            ph_info.append(dict(segs=segs, nqt=sum(seg_n), cuts=cuts, woff=woff, pad=ppad, ooff=ooff))
+        ksplit = max(len(pi["cuts"]) for pi in ph_info)
+        items, item_src = [], []
+        for ks in range(ksplit):
+            for tile in range(v.n_rt * v.n_cg):
+                rt, cgi = tile % v.n_rt, tile // v.n_rt
+                for pi in ph_info:
+                    q0, q1, si, sbase = pi["cuts"][ks]
+                    ccn = pi["segs"][si][1]
+                    items.append([pi["woff"] + (rt * pi["nqt"] + q0) * 256, q1 - q0, ((q0 - sbase) // ccn) | (((q0 - sbase) % ccn) << 8),
+                                  ks * v.l_out * v.sstride + rt * v.rows, cgi * v.nt * v.cols, pi["pad"] | (pi["ooff"] << 8), 0, ccn])
+                    item_src.append(si)
+        if any(len(pi["cuts"]) != ksplit for pi in ph_info):
+            raise ValueError("phases with different K-slice counts are not supported (stale partial tiles)")
+        return items, item_src, ksplit, 0, None, list(srcs)
+
+    def _epilogue_words(self, words: dict, v: _ConvView, dst: Act, all_srcs: List[Act], bias: Optional[torch.Tensor], pbias, *, gn, bwd,
+                        save, emb_off, film, res, pred, bias_row, act, col_norm, cg_real, out_div):
+        """Flags and parameter words of a conv op's epilogue (see `conv`) into `words`; bias, post-bias, gamma and beta join the blob,
+        in that order.  Returns the slots the op (reads, writes): what the LDS plan's liveness is built from."""
+        c_out, l_out, coutp, kpost = v.c_out, v.l_out, v.coutp, words[W2_KPOST]
         if bias_row >= 0:
             assert bias is None, "a table-row bias replaces the static one (fold it into the row)"
             words[W2_BOFF] = bias_row
         else:
             words[W2_BOFF] = self.add(_padded(bias if bias is not None else torch.zeros(c_out, device=self.device), coutp))
-        if xg:
-            words[W2_XG] = xg
-        if gop:
-            words[W2_GMAP] = (l_out.bit_length() - 1) | ((l_out + 2 * HALO2) << 8)
         if kpost:
             words[W2_PBIAS] = self.add(_padded(pbias, coutp))
-        cg = coutp // GROUPS2
-        cg4 = cg // 4
+        cg, cg4 = coutp // GROUPS2, coutp // GROUPS2 // 4
         if cg4 & (cg4 - 1) or cg4 > 32:
             raise ValueError(f"C_out {c_out}: the epilogue partitions at most 1024 channels (8 lane groups x 32 float4 lanes)")
         nk = -(-(cg4 * l_out) // 32)
         if nk > MAX_NK2:
             raise ValueError(f"epilogue: {cg4 * l_out} float4 items per group > {32 * MAX_NK2} (horizon too long for v2)")
         words[W2_CG4_SHIFT], words[W2_NK] = cg4.bit_length() - 1, nk
-        flags = 0
-        reads, writes = list(all_srcs), [dst]
+        flags, reads, writes = 0, list(all_srcs), [dst]
         norm = gn if bwd is None else bwd["gn"]
         if kpost and bwd is not None:
             raise ValueError("post-norm extra convs exist on forward ops only")
@@ -576,10 +648,7 @@ class _Builder2:
             flags |= F2_RES
             words[W2_RES_STRIDE] = res.stride
             reads.append(res)
-        if pred:
-            flags |= F2_PRED
-        if bias_row >= 0:
-            flags |= F2_BIAS_EMB
+        flags |= (F2_PRED if pred else 0) | (F2_BIAS_EMB if bias_row >= 0 else 0)
         if act is not None:
             assert bwd is None and 0 <= act < 15
             flags |= (act + 1) << F2_ACT_SHIFT
@@ -588,17 +657,17 @@ class _Builder2:
             flags |= F2_OUT_DIV
             words[W2_ODIV] = _fbits(float(out_div))
         words[W2_FLAGS] = flags
+        return reads, writes
+
+    def _emit(self, words: dict, acts: dict, items=(), item_src=()):
+        """Append one op: descriptor words, slots (srcs / res / dst / save / dst2 + reads / writes), work items and the source each reads."""
         op = [0] * op_words(self.nw)
         for k, v in words.items():
             op[k] = int(v)
         self.ops.append(op)
-        self.op_acts.append(dict(srcs=list(all_srcs), res=res, dst=dst, save=(save[0] if save is not None else (bwd["save"] if bwd else None)),
-                                 dst2=(bwd.get("dst2") if bwd else None), reads=reads, writes=writes, gop=gop))
-        self.op_items.append(items)
-        self.op_item_src.append(item_src)
-        self.stage = max(self.stage, stage_slices * l_stage * sstride)
-        self.macs += sum(c_out * (l_cols if len(phases) > 1 else l_out) * w.shape[1] * c_in for w, _, _ in phases)
-        return True
+        self.op_acts.append(acts)
+        self.op_items.append(list(items))
+        self.op_item_src.append(list(item_src))
 
     def head(self, src: Act, dst: Act, w1: torch.Tensor, e_off: int, w2: torch.Tensor, b2: Optional[torch.Tensor] = None):
         """Classifier head with its backward in one op (reference nn_classifier/half_jannerunet.py:49-50, :62):
@@ -614,43 +683,26 @@ class _Builder2:
                  # [w2 (hidden) | b2]: the bias only matters for the final log_p forward (cdx_unet2_launch.logp_out)
                  W2_GAMMA: self.add(torch.cat([w2.reshape(-1), (b2 if b2 is not None else w2.new_zeros(1)).reshape(-1)[:1]])), W2_EMB: e_off,
                  W2_COUTP: pad32(c), W2_NK: 1, W2_KSPLIT: 1}
-        op = [0] * op_words(self.nw)
-        for k, v in words.items():
-            op[k] = int(v)
-        self.ops.append(op)
+        self._emit(words, dict(srcs=[], res=src, dst=dst, save=None, dst2=None, reads=[src], writes=[dst]))
         self.head_index = len(self.ops) - 1
-        self.op_acts.append(dict(srcs=[], res=src, dst=dst, save=None, dst2=None, reads=[src], writes=[dst]))
-        self.op_items.append([])
-        self.op_item_src.append([])
         self.stage = max(self.stage, 2 * hidden)
         self.macs += 2 * hidden * c * l
+
+    def _load(self, kind: int, dst: Act):
+        self._emit({W2_KIND: kind, W2_COUT: dst.chans, W2_LOUT: dst.length, W2_NITEMS: 0, W2_DST_STRIDE: dst.stride,
+                    W2_COUTP: pad32(dst.chans), W2_NK: 1, W2_KSPLIT: 1},
+                   dict(srcs=[], res=None, dst=dst, save=None, dst2=None, reads=[], writes=[dst]))
 
     def load_state(self, dst: Act):
         """Compact guided programs: the state x_t is read back from GLOBAL memory (the launch's x_out, where compact programs keep
         it) into a fresh slot for the classifier's first ops -- the denoiser's own copy need not stay in LDS across its peak."""
-        words = {W2_KIND: KIND2_LOADX, W2_COUT: dst.chans, W2_LOUT: dst.length, W2_NITEMS: 0, W2_DST_STRIDE: dst.stride,
-                 W2_COUTP: pad32(dst.chans), W2_NK: 1, W2_KSPLIT: 1}
-        op = [0] * op_words(self.nw)
-        for k, v in words.items():
-            op[k] = int(v)
-        self.ops.append(op)
-        self.op_acts.append(dict(srcs=[], res=None, dst=dst, save=None, dst2=None, reads=[], writes=[dst]))
-        self.op_items.append([])
-        self.op_item_src.append([])
+        self._load(KIND2_LOADX, dst)
 
     def load_context(self, dst: Act):
         """Batch-tiled MLP programs: the per-sample condition features of the workgroup's samples (launch `ctx`, (batch, tile, C)) ->
         slot `dst` at the start of every forward; zeros for the unconditional forward of a classifier-free-guidance pair and when the
         request has no condition (the reference substitutes zeros, e.g. pearcemlp.py:59-60)."""
-        words = {W2_KIND: KIND2_LOADC, W2_COUT: dst.chans, W2_LOUT: dst.length, W2_NITEMS: 0, W2_DST_STRIDE: dst.stride,
-                 W2_COUTP: pad32(dst.chans), W2_NK: 1, W2_KSPLIT: 1}
-        op = [0] * op_words(self.nw)
-        for k, v in words.items():
-            op[k] = int(v)
-        self.ops.append(op)
-        self.op_acts.append(dict(srcs=[], res=None, dst=dst, save=None, dst2=None, reads=[], writes=[dst]))
-        self.op_items.append([])
-        self.op_item_src.append([])
+        self._load(KIND2_LOADC, dst)
 
     def plan_arena(self, base: int) -> int:
         """Interval allocation of the non-persistent slots over op liveness; patches slot offsets into the ops.  `alias_residual`:
@@ -771,34 +823,35 @@ def _emb_table_spec(b: "_Builder2", net, blocks, dev, raw_rows: Optional[Tuple[t
     return emb
 
 
-def _lower_janner(b: "_Builder2", net, horizon: int, x: Act):
-    """Ops of one JannerUNet1d forward (reference nn_diffusion/jannerunet.py:154-201) reading slot `x`; returns (pred slot, blocks)."""
-    d, k, md = net.in_dim, net.kernel_size, net.model_dim
-    blocks = []
-
-    def resblock(srcs: List[Act], rb) -> Act:
-        """ResidualBlock (jannerunet.py:51-69) over the channel concat of `srcs`."""
-        c_out, length = rb.conv1[0].out_channels, srcs[0].length
-        e_off = b.emb_slot(c_out)
-        blocks.append((rb, e_off))
-        t1 = b.act(length, c_out)
-        b.conv(srcs, t1, _conv1d_eff(rb.conv1[0]), rb.conv1[0].bias, pad=k // 2, gn=rb.conv1[1], emb_off=e_off)
-        out = b.act(length, c_out)
-        if isinstance(rb.residual_conv, nn.Identity):
-            assert len(srcs) == 1
-            b.conv([t1], out, _conv1d_eff(rb.conv2[0]), rb.conv2[0].bias, pad=k // 2, gn=rb.conv2[1], res=srcs[0])
-        else:
-            # the 1x1 skip conv rides in the second conv's op when that pays: its work items take some of the waves, its partial tiles
-            # are added after the norm / activation (one op, two barriers and one epilogue less per block)
-            fused = FUSE_SKIP and b.conv([t1], out, _conv1d_eff(rb.conv2[0]), rb.conv2[0].bias, pad=k // 2, gn=rb.conv2[1], extra=[
-                dict(srcs=srcs, w_eff=_conv1d_eff(rb.residual_conv), pad=0, bias=rb.residual_conv.bias, post=True)])
-            if not fused:
-                b.conv([t1], out, _conv1d_eff(rb.conv2[0]), rb.conv2[0].bias, pad=k // 2, gn=rb.conv2[1])
-                b.conv(srcs, out, _conv1d_eff(rb.residual_conv), rb.residual_conv.bias, res=out)     # out += W_r x + b_r
+def _resblock_ops(b: "_Builder2", srcs: List[Act], rb, *, pad: int, e_off: int, film: bool = False, save1=None, save2=None) -> Act:
+    """Ops of a ResidualBlock (reference jannerunet.py:51-69, chiunet.py:17-46, half_jannerunet.py) over the channel concat of `srcs`:
+    conv1 (GroupNorm, Mish, + the table row at `e_off` / `film`: scale * y + bias), then conv2 + the skip path.  An identity skip is
+    conv2's residual slot.  A 1x1 skip conv rides in the second conv's op when that pays: its work items take some of the waves, its
+    partial tiles are added after the norm / activation (one op, two barriers and one epilogue less per block); else it is an op of
+    its own that accumulates into the block's output (out += W_r x + b_r).  `save1` / `save2`: the GroupNorms' (save slot, stats index)."""
+    c_out, length = rb.conv1[0].out_channels, srcs[0].length
+    t1 = b.act(length, c_out)
+    b.conv(srcs, t1, _conv1d_eff(rb.conv1[0]), rb.conv1[0].bias, pad=pad, gn=rb.conv1[1], emb_off=e_off, film=film, save=save1)
+    out = b.act(length, c_out)
+    w2, b2, conv2 = _conv1d_eff(rb.conv2[0]), rb.conv2[0].bias, dict(pad=pad, gn=rb.conv2[1], save=save2)
+    if isinstance(rb.residual_conv, nn.Identity):
+        assert len(srcs) == 1
+        b.conv([t1], out, w2, b2, res=srcs[0], **conv2)
         return out
+    wr, br = _conv1d_eff(rb.residual_conv), rb.residual_conv.bias
+    if not (FUSE_SKIP and b.conv([t1], out, w2, b2, extra=[dict(srcs=srcs, w_eff=wr, pad=0, bias=br, post=True)], **conv2)):
+        b.conv([t1], out, w2, b2, **conv2)
+        b.conv(srcs, out, wr, br, res=out)
+    return out
 
+
+def _lower_unet(b: "_Builder2", x: Act, horizon: int, downs, mids, ups, final_conv, pad: int, resblock) -> Act:
+    """The U-Net walk both temporal U-Nets share (reference jannerunet.py:154-201, chiunet.py:152-192) reading slot `x`: down levels
+    (two blocks, stride-2 conv), mid blocks, up levels (two blocks over the concat with the level's skip, ConvTranspose1d(4, 2, 1)),
+    then final_conv's Conv1dBlock with padding `pad`.  `downs` / `ups`: (res1, res2, resample) per level; `mids`: lists of blocks;
+    `resblock(srcs, rb) -> Act` lowers one block.  Returns the last hidden slot."""
     cur, skips = x, []
-    for res1, res2, _, down in net.downs:
+    for res1, res2, down in downs:
         cur = resblock([resblock([cur], res1)], res2)
         skips.append(cur)
         if not isinstance(down, nn.Identity):
@@ -807,8 +860,10 @@ def _lower_janner(b: "_Builder2", net, horizon: int, x: Act):
             nxt = b.act((cur.length - 1) // 2 + 1, cur.chans)
             b.conv([cur], nxt, _conv1d_eff(down.conv), down.conv.bias, stride=2, pad=1)
             cur = nxt
-    cur = resblock([resblock([cur], net.mid_block1)], net.mid_block2)
-    for res1, res2, _, up in net.ups:
+    for blocks in mids:
+        for rb in blocks:
+            cur = resblock([cur], rb)
+    for res1, res2, up in ups:
         cur = resblock([resblock([cur, skips.pop()], res1)], res2)
         if not isinstance(up, nn.Identity):
             nxt = b.act(cur.length * 2, cur.chans)
@@ -816,12 +871,27 @@ def _lower_janner(b: "_Builder2", net, horizon: int, x: Act):
             cur = nxt
     if cur.length != horizon:
         raise ValueError("up path does not return to the input horizon")
-    fc = net.final_conv
-    if cur.chans != fc[0].in_channels:
+    t = b.act(horizon, final_conv[0].out_channels)
+    b.conv([cur], t, _conv1d_eff(final_conv[0]), final_conv[0].bias, pad=pad, gn=final_conv[1])
+    return t
+
+
+def _lower_janner(b: "_Builder2", net, horizon: int, x: Act):
+    """Ops of one JannerUNet1d forward (reference nn_diffusion/jannerunet.py:154-201) reading slot `x`; returns (last hidden slot,
+    final_conv, [(block, table offset)])."""
+    k, fc, blocks = net.kernel_size, net.final_conv, []
+    last = net.ups[-1][1] if len(net.ups) else net.mid_block2
+    if last.conv1[0].out_channels != fc[0].in_channels:
         # dim_mult[0] != 1: the reference's own forward fails on this net (jannerunet.py:139-144 builds final_conv on model_dim)
-        raise ValueError(f"final conv expects {fc[0].in_channels} channels, the up path ends with {cur.chans}")
-    t = b.act(horizon, md)
-    b.conv([cur], t, _conv1d_eff(fc[0]), fc[0].bias, pad=2, gn=fc[1])
+        raise ValueError(f"final conv expects {fc[0].in_channels} channels, the up path ends with {last.conv1[0].out_channels}")
+
+    def resblock(srcs: List[Act], rb) -> Act:
+        e_off = b.emb_slot(rb.conv1[0].out_channels)
+        blocks.append((rb, e_off))
+        return _resblock_ops(b, srcs, rb, pad=k // 2, e_off=e_off)
+
+    t = _lower_unet(b, x, horizon, [(r1, r2, down) for r1, r2, _, down in net.downs], [[net.mid_block1, net.mid_block2]],
+                    [(r1, r2, up) for r1, r2, _, up in net.ups], fc, 2, resblock)
     return t, fc, blocks
 
 
@@ -829,52 +899,16 @@ def _lower_chiunet(b: "_Builder2", net, horizon: int, x: Act):
     """Ops of one ChiUNet1d forward with a global condition (reference nn_diffusion/chiunet.py:152-192) reading slot `x`; returns
     (last hidden slot, final_conv, [(block, table offset)]).  A block's FiLM vector Linear(Mish(emb)) (chiunet.py:36-45) is a row of
     the launch's per-(step, trajectory) table, like JannerUNet1d's time vectors; with cond_predict_scale the row holds [scale | bias]."""
-    k = net.final_conv[0].kernel_size[0]
-    blocks = []
+    k, blocks = net.final_conv[0].kernel_size[0], []
 
     def resblock(srcs: List[Act], rb) -> Act:
-        c_out, length = rb.out_dim, srcs[0].length
         film = bool(rb.cond_predict_scale)
-        e_off = b.emb_slot(c_out, film)
+        e_off = b.emb_slot(rb.out_dim, film)
         blocks.append((rb, e_off))
-        t1 = b.act(length, c_out)
-        b.conv(srcs, t1, _conv1d_eff(rb.conv1[0]), rb.conv1[0].bias, pad=k // 2, gn=rb.conv1[1], emb_off=e_off, film=film)
-        out = b.act(length, c_out)
-        if isinstance(rb.residual_conv, nn.Identity):
-            assert len(srcs) == 1
-            b.conv([t1], out, _conv1d_eff(rb.conv2[0]), rb.conv2[0].bias, pad=k // 2, gn=rb.conv2[1], res=srcs[0])
-        else:
-            fused = FUSE_SKIP and b.conv([t1], out, _conv1d_eff(rb.conv2[0]), rb.conv2[0].bias, pad=k // 2, gn=rb.conv2[1], extra=[
-                dict(srcs=srcs, w_eff=_conv1d_eff(rb.residual_conv), pad=0, bias=rb.residual_conv.bias, post=True)])
-            if not fused:
-                b.conv([t1], out, _conv1d_eff(rb.conv2[0]), rb.conv2[0].bias, pad=k // 2, gn=rb.conv2[1])
-                b.conv(srcs, out, _conv1d_eff(rb.residual_conv), rb.residual_conv.bias, res=out)
-        return out
+        return _resblock_ops(b, srcs, rb, pad=k // 2, e_off=e_off, film=film)
 
-    cur, skips = x, []
-    for res1, res2, down in net.downs:
-        cur = resblock([resblock([cur], res1)], res2)
-        skips.append(cur)
-        if not isinstance(down, nn.Identity):
-            if cur.length % 2:
-                raise ValueError("horizon too short for the number of resolutions")
-            nxt = b.act((cur.length - 1) // 2 + 1, cur.chans)
-            b.conv([cur], nxt, _conv1d_eff(down.conv), down.conv.bias, stride=2, pad=1)
-            cur = nxt
-    for mid in net.mids:
-        cur = resblock([cur], mid)
-    for res1, res2, up in net.ups:
-        cur = resblock([resblock([cur, skips.pop()], res1)], res2)
-        if not isinstance(up, nn.Identity):
-            nxt = b.act(cur.length * 2, cur.chans)
-            b.conv([cur], nxt, _convT1d_eff(up.conv), up.conv.bias, stride=2, pad=1, transposed=True)
-            cur = nxt
-    if cur.length != horizon:
-        raise ValueError("up path does not return to the input horizon")
-    fc = net.final_conv
-    t = b.act(horizon, net.model_dim)
-    b.conv([cur], t, _conv1d_eff(fc[0]), fc[0].bias, pad=k // 2, gn=fc[1])
-    return t, fc, blocks
+    t = _lower_unet(b, x, horizon, net.downs, [list(net.mids)], net.ups, net.final_conv, k // 2, resblock)
+    return t, net.final_conv, blocks
 
 
 def chiunet_film_spec(net, blocks, n_emb: int, dev) -> dict:
@@ -912,12 +946,8 @@ def compile_chiunet2(net, horizon: int, max_lds_bytes: int = 160 * 1024, allow_4
     why = supports_chiunet2(net)
     if why is not None:
         raise ValueError(why)
-    dev = next(net.parameters()).device
-    b = _Builder2(dev, nw)
-    b.allow_4x4 = allow_4x4
-    b.alias_residual = compact
-    if max_stage is not None:
-        b.max_stage = max_stage
+    b = _unet_builder(net, nw, allow_4x4=allow_4x4, compact=compact, max_stage=max_stage)
+    dev = b.device
     d = net.final_conv[3].out_channels
     x = b.act(horizon, d, persistent=True)
     t, fc, blocks = _lower_chiunet(b, net, horizon, x)
@@ -970,6 +1000,15 @@ def _lin_eff2(w: torch.Tensor) -> torch.Tensor:
     return w.detach().unsqueeze(1)
 
 
+def _start_mlp(net, tile: int, nw: int, d: int, n_cond: int):
+    """Builder, table-row bookkeeping, device, persistent state slot and context slot (reloaded by op 0) of an MLP program."""
+    dev = next(net.parameters()).device
+    b = _Builder2(dev, nw)
+    x, ctx = b.act(tile, d, persistent=True), b.act(tile, n_cond, persistent=True)
+    b.load_context(ctx)
+    return b, _RowSpec(b), dev, x, ctx
+
+
 def _finish_mlp(b: "_Builder2", rows: _RowSpec, kind: str, x: Act, pred: Act, ctx: Optional[Act], tile: int, d: int, emb_dim: int,
                 max_lds_bytes: int, dev) -> Program2:
     prog = _finalize2(b, [{}], x, pred, tile, d, emb_dim, max_lds_bytes, [ctx] if ctx is not None else [])
@@ -987,10 +1026,8 @@ def compile_pearce_mlp2(net, tile: int, max_lds_bytes: int = 160 * 1024, nw: int
     PADDED hidden layout: group g sits at channels [G g, G g + 24) of a 8 G-wide slot (G = 32), the pad channels have zero weights, bias,
     gamma and beta -- they hold exact zeros through norm, GELU, skip and division -- and stay out of the variance (W2_CGREAL4)."""
     from .consts import ACT_GELU_ERF, ACT_LEAKY, ACT_NONE
-    dev = next(net.parameters()).device
-    b = _Builder2(dev, nw)
-    rows = _RowSpec(b)
     d, e, hd, n_cond = net.act_dim, net.emb_dim, net.hidden_dim, net.To * net.emb_dim
+    b, rows, dev, x, ctx = _start_mlp(net, tile, nw, d, n_cond)
     gn0 = net.fcs[0].model[1]
     n_grp = gn0.num_groups
     if hd % n_grp or (hd // n_grp) % 4:
@@ -1023,9 +1060,6 @@ def compile_pearce_mlp2(net, tile: int, max_lds_bytes: int = 160 * 1024, nw: int
             self.num_groups, self.eps = GROUPS2 if hp != hd else gn.num_groups, gn.eps
             self.weight, self.bias = out_rows(gn.weight.detach()), out_rows(gn.bias.detach())
     creal = cg_real if hp != hd else 0
-    x = b.act(tile, d, persistent=True)
-    ctx = b.act(tile, n_cond, persistent=True)
-    b.load_context(ctx)
     a1, xe = b.act(tile, e), b.act(tile, e)
     b.conv([x], a1, _lin_eff2(net.act_emb[0].weight), net.act_emb[0].bias, act=ACT_LEAKY)
     b.conv([a1], xe, _lin_eff2(net.act_emb[2].weight), net.act_emb[2].bias, act=ACT_NONE)
@@ -1054,15 +1088,10 @@ def compile_dql_mlp2(net, tile: int, max_lds_bytes: int = 160 * 1024, nw: int = 
     """DQLMlp (reference nn_diffusion/dqlmlp.py:9-52) and DVInvMlp (dvinvmlp.py:9-47, same trunk): features [x | time_mlp(map_noise(t))
     | obs] -> 3 x (Linear, Mish) -> Linear; the time features are batch-invariant: they enter as the first layer's bias row."""
     from .consts import ACT_MISH, ACT_NONE
-    dev = next(net.parameters()).device
-    b = _Builder2(dev, nw)
-    rows = _RowSpec(b)
     d, e, obs = net.final_layer.out_features, net.time_mlp[0].in_features, net.obs_dim
+    b, rows, dev, x, ctx = _start_mlp(net, tile, nw, d, obs)
     m = net.mid_layer
     hid = m[0].out_features
-    x = b.act(tile, d, persistent=True)
-    ctx = b.act(tile, obs, persistent=True)
-    b.load_context(ctx)
     w0 = m[0].weight.detach()
     m1, m2, m3 = b.act(tile, hid), b.act(tile, hid), b.act(tile, hid)
     b.conv([x, ctx], m1, _lin_eff2(torch.cat([w0[:, :d], w0[:, d + e:]], 1)), None, act=ACT_MISH,
@@ -1078,19 +1107,14 @@ def compile_mlp_nn2(net, tile: int, max_lds_bytes: int = 160 * 1024, nw: int = N
     """MlpNNDiffusion (reference nn_diffusion/mlps.py:10-40): Mlp(cat[x, map_noise(t) + condition]); the first Linear's embedding
     columns act on the time embedding (bias row) and on the condition (context slot) alike."""
     from .consts import _act_id
-    dev = next(net.parameters()).device
-    b = _Builder2(dev, nw)
-    rows = _RowSpec(b)
     layers = list(net.mlp.mlp)
     lins = [m[0] if isinstance(m, nn.Sequential) else m for m in layers if isinstance(m, (nn.Sequential, nn.Linear))]
     acts = [_act_id(m[1]) for m in layers if isinstance(m, nn.Sequential)] + [_act_id(layers[-1])]
     if any(a is None for a in acts) or len(lins) != len(acts):
         raise ValueError("MlpNNDiffusion: activation without a native epilogue")
     d = lins[-1].out_features
-    e = lins[0].in_features - d
-    x = b.act(tile, d, persistent=True)
-    ctx = b.act(tile, e, persistent=True)
-    b.load_context(ctx)
+    b, rows, dev, x, ctx = _start_mlp(net, tile, nw, d, lins[0].in_features - d)
+    e = ctx.chans
     cur, pred = None, None
     for i, (lin, act) in enumerate(zip(lins, acts)):
         last = i == len(lins) - 1
@@ -1110,14 +1134,9 @@ def compile_sfbc_unet2(net, tile: int, max_lds_bytes: int = 160 * 1024, nw: int 
     t_layer(map_noise(t)) + condition.  Lc t_layer(...) + bc is a per-step vector added after the first activation (table row);
     Lc condition and the skip Linear are 1-tap convs whose partial tiles are added after the activation of the op they ride in."""
     from .consts import ACT_NONE, ACT_SILU
-    dev = next(net.parameters()).device
-    b = _Builder2(dev, nw)
-    b.fuse_max = 1 << 30                  # (Linears: the extra streams are what the block IS, not an optimisation)
-    rows = _RowSpec(b)
     d, e = net.out_layer.out_features, net.t_layer[0].in_features
-    x = b.act(tile, d, persistent=True)
-    ctx = b.act(tile, e, persistent=True)
-    b.load_context(ctx)
+    b, rows, dev, x, ctx = _start_mlp(net, tile, nw, d, e)
+    b.fuse_max = 1 << 30                  # (Linears: the extra streams are what the block IS, not an optimisation)
 
     def block(srcs: List[Act], blk) -> Act:
         c_out = blk.linear1[0].out_features
@@ -1165,7 +1184,7 @@ def _lower_half_janner_grad(b: "_Builder2", clf, horizon: int, x: Act, grad: Opt
     """Forward AND backward-data pass of a HalfJannerUNet1d classifier (reference nn_classifier/half_jannerunet.py:102-125) reading
     slot `x`: d out / d x -> slot `grad` (what BaseClassifier.gradients returns, classifier/base.py:74-79, for the summed log p).
     Every GroupNorm layer saves its normalised values + rstd on the way up; on the way down each backward-data conv's epilogue applies
-    the backward of the (GroupNorm -> Mish) below it.  Returns the (block, emb offset) list and the head's table offset.
+    the backward of the (GroupNorm -> Mish) below it.  Returns the (block, emb offset) list and the head's table rows (`_emb_table_spec`).
     `forward_only`: the forward ops and the head only, nothing saved (the classifier's own program: log p of a batch)."""
     if clf.norm_type != "groupnorm" or clf.out_dim != 1:
         raise ValueError("the fused classifier gradient needs norm_type='groupnorm' and out_dim == 1")
@@ -1179,18 +1198,8 @@ def _lower_half_janner_grad(b: "_Builder2", clf, horizon: int, x: Act, grad: Opt
         e_off = b.emb_slot(c_out)
         blocks.append((rb, e_off))
         s1, s2 = (None, None) if forward_only else ((b.save_slot(length, c_out), b.stats_slot()), (b.save_slot(length, c_out), b.stats_slot()))
-        t1 = b.act(length, c_out)
-        b.conv([src], t1, _conv1d_eff(rb.conv1[0]), rb.conv1[0].bias, pad=ksz // 2, gn=rb.conv1[1], emb_off=e_off, save=s1)
-        out = b.act(length, c_out)
-        ident = isinstance(rb.residual_conv, nn.Identity)
-        fused = (not ident) and FUSE_SKIP and b.conv(
-            [t1], out, _conv1d_eff(rb.conv2[0]), rb.conv2[0].bias, pad=ksz // 2, gn=rb.conv2[1], save=s2,
-            extra=[dict(srcs=[src], w_eff=_conv1d_eff(rb.residual_conv), pad=0, bias=rb.residual_conv.bias, post=True)])
-        if not fused:
-            b.conv([t1], out, _conv1d_eff(rb.conv2[0]), rb.conv2[0].bias, pad=ksz // 2, gn=rb.conv2[1], res=src if ident else None, save=s2)
-            if not ident:
-                b.conv([src], out, _conv1d_eff(rb.residual_conv), rb.residual_conv.bias, res=out)
-        tape.append(("block", rb, ksz, src, s1, s2, ident))
+        out = _resblock_ops(b, [src], rb, pad=ksz // 2, e_off=e_off, save1=s1, save2=s2)
+        tape.append(("block", rb, ksz, src, s1, s2, isinstance(rb.residual_conv, nn.Identity)))
         return out
 
     def down(src: Act, dn) -> Act:
@@ -1217,19 +1226,17 @@ def _lower_half_janner_grad(b: "_Builder2", clf, horizon: int, x: Act, grad: Opt
     g = b.act(cur.length, cur.chans)                       # gradient w.r.t. the last downsample's output
     b.head(cur, g, lin1.weight.detach()[:, :fc].reshape(lin1.out_features, cur.chans, cur.length), head_off, lin2.weight.detach(),
            lin2.bias.detach() if lin2.bias is not None else None)
+    raw_rows = (lin1.weight.detach()[:, fc:], lin1.bias.detach(), head_off)       # the head's share of the table: W1e emb + b1
     if forward_only:
-        return blocks, (lin1, head_off)
+        return blocks, raw_rows
 
     # ---- backward: g = gradient w.r.t. the output of the tape entry on top ----
     # what lies BELOW an entry decides the epilogue of the op that completes the gradient w.r.t. that entry's input: another
     # block's output (a residual sum: keep the plain gradient for the skip path AND push it through that block's conv2 norm),
     # a downsample's output or the network input (plain)
-    def lower_entry(idx: int):
-        return tape[idx - 1] if idx > 0 else None
-
     def finish(idx: int, make_op):
         """Emit the op that completes the gradient w.r.t. tape[idx]'s input; returns (plain gradient slot, pre-norm gradient slot)."""
-        below = lower_entry(idx)
+        below = tape[idx - 1] if idx > 0 else None
         src_act = tape[idx][3] if tape[idx][0] == "block" else tape[idx][2]
         if below is not None and below[0] == "block":
             _, rb_b, _, _, _, s2_b, _ = below
@@ -1271,7 +1278,7 @@ def _lower_half_janner_grad(b: "_Builder2", clf, horizon: int, x: Act, grad: Opt
                 b.conv([gout], skip, wrt, None)                                             # W_r^T g_out
                 b.conv([gu1], dst, _dgrad_eff(rb.conv1[0]), None, pad=ksz // 2, res=skip, bwd=bw)
             g_plain, g_u2 = finish(idx, make)
-    return blocks, (lin1, head_off)
+    return blocks, raw_rows
 
 
 def compile_classifier2(clf, horizon: int, max_lds_bytes: int = 160 * 1024, nw: int = NW2_MAX) -> Program2:
@@ -1282,9 +1289,8 @@ def compile_classifier2(clf, horizon: int, max_lds_bytes: int = 160 * 1024, nw: 
     b = _Builder2(dev, nw)
     d = clf.in_dim
     x = b.act(horizon, d, persistent=True)
-    blocks, (lin1, head_off) = _lower_half_janner_grad(b, clf, horizon, x, None, forward_only=True)
-    fcw = lin1.in_features - clf.model_dim
-    emb = _emb_table_spec(b, clf, blocks, dev, raw_rows=(lin1.weight.detach()[:, fcw:], lin1.bias.detach(), head_off))
+    blocks, raw_rows = _lower_half_janner_grad(b, clf, horizon, x, None, forward_only=True)
+    emb = _emb_table_spec(b, clf, blocks, dev, raw_rows=raw_rows)
     out = b.op_acts[b.head_index]["dst"]                   # (the head's gradient slot: never written by the log_p pass)
     prog = _finalize2(b, [emb], x, out, horizon, d, clf.emb_dim, max_lds_bytes, [])
     prog.meta["cls_first"], prog.meta["head_op"] = 0, b.head_index
@@ -1336,6 +1342,24 @@ def _finalize2(b: "_Builder2", nets_emb: List[dict], x: Act, pred: Act, horizon:
                     compact=compact, ws_floats=((horizon * d + 3) // 4 * 4) if compact else 0)
 
 
+def _unet_builder(net, nw: int, *, allow_4x4: bool = True, compact: bool = False, max_stage: Optional[int] = None,
+                  member: Tuple[int, int] = (0, 1), grouped: bool = False, alias_residual: Optional[bool] = None,
+                  what: str = "split / grouped programs") -> _Builder2:
+    """The configured builder of a U-Net program (`compile_janner2`, `compile_chiunet2`, `compile_guided2`).  `member` = (m, k) with
+    k > 1: member m's view of a split or `grouped` program named `what`."""
+    b = _Builder2(next(net.parameters()).device, nw)
+    b.allow_4x4 = allow_4x4
+    b.alias_residual = compact if alias_residual is None else alias_residual
+    b.member, b.grouped = member, grouped
+    if member[1] > 1:
+        if compact or nw != NW2_MAX:
+            raise ValueError(f"{what}: the 8-wave, state-in-LDS form only")
+        b.fuse_max = 1 << 30                  # (a member's K slices are short: the 1x1 skips always ride in their block's second conv)
+    if max_stage is not None:
+        b.max_stage = max_stage
+    return b
+
+
 def compile_janner2(net, horizon: int, max_lds_bytes: int = 160 * 1024, allow_4x4: bool = True, nw: int = NW2, compact: bool = False,
                     max_stage: Optional[int] = None, member: Tuple[int, int] = (0, 1), grouped: bool = False,
                     alias_residual: Optional[bool] = None) -> Program2:
@@ -1344,28 +1368,37 @@ def compile_janner2(net, horizon: int, max_lds_bytes: int = 160 * 1024, allow_4x
     why = supports_janner(net)
     if why is not None:
         raise ValueError(why)
-    dev = next(net.parameters()).device
-    b = _Builder2(dev, nw)
-    b.allow_4x4 = allow_4x4
-    b.alias_residual = compact if alias_residual is None else alias_residual
-    b.member = member
-    b.grouped = grouped
-    if member[1] > 1:
-        if compact or nw != NW2_MAX:
-            raise ValueError("split / grouped programs: the 8-wave, state-in-LDS form only")
-        b.fuse_max = 1 << 30                  # (a member's K slices are short: the 1x1 skips always ride in their block's second conv)
-    if max_stage is not None:
-        b.max_stage = max_stage
+    b = _unet_builder(net, nw, allow_4x4=allow_4x4, compact=compact, max_stage=max_stage, member=member, grouped=grouped,
+                      alias_residual=alias_residual)
     d = net.in_dim
     x = b.act(horizon, d, persistent=True)
     t, fc, blocks = _lower_janner(b, net, horizon, x)
     pred = b.act(horizon, d)                 # arena slot: written by the last op, read by the solver step right after it
     b.conv([t], pred, _conv1d_eff(fc[3]), fc[3].bias, pred=True)
-    emb = _emb_table_spec(b, net, blocks, dev)
+    emb = _emb_table_spec(b, net, blocks, b.device)
     prog = _finalize2(b, [emb], x, pred, horizon, d, net.emb_dim, max_lds_bytes, [], compact=compact)
     prog.meta["xchg_floats"] = b.xchg_floats
     prog.meta["n_gops"] = sum(1 for oa in b.op_acts if oa.get("gop"))
     return prog
+
+
+def _compile_members(make_member, k: int, grouped: bool, what: Optional[str] = None) -> Program2:
+    """One program out of the k member views `make_member(m, alias_residual)` of a split or a `grouped` program; `what` names the
+    grouped program and its network in the refusal of a net without a single op worth grouping."""
+    if k not in (2, 4):
+        raise ValueError("group size 2 or 4" if grouped else "split factor 2 or 4")
+    if not grouped:
+        return _merge_members([make_member(m, None) for m in range(k)], k)
+    try:                                              # in-place residual outputs only if the plain plan does not fit
+        members = [make_member(m, False) for m in range(k)]
+    except ValueError:
+        members = [make_member(m, True) for m in range(k)]
+    p0 = _merge_members(members, k)
+    p0.meta["group_k"] = k
+    del p0.meta["split_k"]
+    if p0.meta["n_gops"] == 0:
+        raise ValueError(f"{what} streams enough weights to be grouped")
+    return p0
 
 
 def compile_janner2_split(net, horizon: int, k: int, max_lds_bytes: int = 160 * 1024) -> Program2:
@@ -1374,10 +1407,8 @@ def compile_janner2_split(net, horizon: int, k: int, max_lds_bytes: int = 160 * 
     can be cut that way; after such an op the members all-gather the op's output through a 4 KB tile in global memory (same L2: no
     agent-scope fence, tools/xwg_exchange_probe.hip).  The k member views share the blob, the LDS plan and the op count; their
     descriptors are laid out [member 0 ops | member 1 ops | ... | item tails], so member m's op i is descriptor m * n_ops + i."""
-    if k not in (2, 4):
-        raise ValueError("split factor 2 or 4")
-    members = [compile_janner2(net, horizon, max_lds_bytes=max_lds_bytes, nw=NW2_MAX, member=(m, k)) for m in range(k)]
-    return _merge_members(members, k)
+    return _compile_members(lambda m, alias: compile_janner2(net, horizon, max_lds_bytes=max_lds_bytes, nw=NW2_MAX, member=(m, k)),
+                            k, False)
 
 
 def _merge_members(members: List[Program2], k: int) -> Program2:
@@ -1417,23 +1448,9 @@ def compile_janner2_group(net, horizon: int, k: int, max_lds_bytes: int = 160 * 
     members all-gather its output through the group's tile in L2 (the exchange of the split programs), and an ordinary op that feeds a
     grouped one publishes its whole trajectory the same way.  Descriptor layout as for split programs: [member 0 ops | member 1 ops | ...
     | item tails]."""
-    if k not in (2, 4):
-        raise ValueError("group size 2 or 4")
-    members = None
-    for alias in (False, True):                       # in-place residual outputs only if the plain plan does not fit
-        try:
-            members = [compile_janner2(net, horizon, max_lds_bytes=max_lds_bytes, nw=NW2_MAX, member=(m, k), grouped=True,
-                                       alias_residual=alias) for m in range(k)]
-            break
-        except ValueError:
-            if alias:
-                raise
-    p0 = _merge_members(members, k)
-    p0.meta["group_k"] = k
-    del p0.meta["split_k"]
-    if p0.meta["n_gops"] == 0:
-        raise ValueError("grouped program: no op of this net streams enough weights to be grouped")
-    return p0
+    return _compile_members(lambda m, alias: compile_janner2(net, horizon, max_lds_bytes=max_lds_bytes, nw=NW2_MAX, member=(m, k),
+                                                             grouped=True, alias_residual=alias),
+                            k, True, "grouped program: no op of this net")
 
 
 def compile_guided2(net, clf, horizon: int, max_lds_bytes: int = 160 * 1024, nw: int = NW2_MAX, save_global: bool = False,
@@ -1447,18 +1464,11 @@ def compile_guided2(net, clf, horizon: int, max_lds_bytes: int = 160 * 1024, nw:
         raise ValueError(why)
     if clf.in_dim != net.in_dim:
         raise ValueError("classifier and denoiser disagree on the state dimension")
-    dev = next(net.parameters()).device
-    b = _Builder2(dev, nw)
+    # (member views of a GROUPED / SPLIT guided program: compile_guided2_group / _split)
+    b = _unet_builder(net, nw, compact=compact, max_stage=max_stage, member=member, grouped=grouped, alias_residual=alias_residual,
+                      what="grouped / split guided programs")
     b.save_global = save_global          # saved x_hat tensors in global memory: the LDS plan shrinks enough for two trajectories
-    if max_stage is not None:
-        b.max_stage = max_stage
-    b.alias_residual = compact if alias_residual is None else alias_residual
-    b.member, b.grouped = member, grouped
-    if member[1] > 1:                    # member view of a GROUPED / SPLIT guided program (compile_guided2_group / _split)
-        if compact or nw != NW2_MAX:
-            raise ValueError("grouped / split guided programs: the 8-wave, state-in-LDS form only")
-        b.fuse_max = 1 << 30
-    d = net.in_dim
+    dev, d = b.device, net.in_dim
     if compact:
         b.ws_floats = (horizon * d + 3) // 4 * 4         # workspace of a trajectory: [multistep memory | saved tensors]
     x = b.act(horizon, d, persistent=True)
@@ -1477,9 +1487,8 @@ def compile_guided2(net, clf, horizon: int, max_lds_bytes: int = 160 * 1024, nw:
         # memory, the denoiser's LDS copy of x_t dies with its first op, and the classifier gets its own copy through a load op
         xc = b.act(horizon, d)
         b.load_state(xc)
-    cblocks, (lin1, head_off) = _lower_half_janner_grad(b, clf, horizon, xc, grad)
-    fcw = lin1.in_features - clf.model_dim
-    emb_clf = _emb_table_spec(b, clf, cblocks, dev, raw_rows=(lin1.weight.detach()[:, fcw:], lin1.bias.detach(), head_off))
+    cblocks, raw_rows = _lower_half_janner_grad(b, clf, horizon, xc, grad)
+    emb_clf = _emb_table_spec(b, clf, cblocks, dev, raw_rows=raw_rows)
     prog = _finalize2(b, [emb_den, emb_clf], x, pred, horizon, d, net.emb_dim, max_lds_bytes, [], grad=grad, compact=compact)
     prog.meta["n_den"] = n_den
     prog.meta["cls_first"], prog.meta["head_op"] = n_den, b.head_index      # final log_p forward: ops [cls_first, head_op] once more
@@ -1493,10 +1502,7 @@ def compile_guided2_split(net, clf, horizon: int, k: int, max_lds_bytes: int = 1
     """The guided program for SMALL batches (B x k <= 256 workgroups): one trajectory over k workgroups of an XCD as in
     `compile_janner2_split` -- the DENOISER's ops that can be cut by row tiles are, with an all-gather behind each; the classifier's
     forward / backward ops, the solver step and the final log_p pass are computed by every member on its own copy of the trajectory."""
-    if k not in (2, 4):
-        raise ValueError("split factor 2 or 4")
-    members = [compile_guided2(net, clf, horizon, max_lds_bytes=max_lds_bytes, member=(m, k)) for m in range(k)]
-    return _merge_members(members, k)
+    return _compile_members(lambda m, alias: compile_guided2(net, clf, horizon, max_lds_bytes=max_lds_bytes, member=(m, k)), k, False)
 
 
 def compile_guided2_group(net, clf, horizon: int, k: int, max_lds_bytes: int = 160 * 1024, save_global: bool = False) -> Program2:
@@ -1505,20 +1511,6 @@ def compile_guided2_group(net, clf, horizon: int, k: int, max_lds_bytes: int = 1
     L2; every other op -- the rest of the denoiser, the classifier's forward and backward ops with their saved tensors, the solver
     step, the final log_p pass -- runs on the member's own trajectory as in the ordinary guided program (`cdx_unet2_kernel<1, 8, true,
     ..., split>`)."""
-    if k not in (2, 4):
-        raise ValueError("group size 2 or 4")
-    members = None
-    for alias in (False, True):
-        try:
-            members = [compile_guided2(net, clf, horizon, max_lds_bytes=max_lds_bytes, member=(m, k), grouped=True, alias_residual=alias,
-                                       save_global=save_global) for m in range(k)]
-            break
-        except ValueError:
-            if alias:
-                raise
-    p0 = _merge_members(members, k)
-    p0.meta["group_k"] = k
-    del p0.meta["split_k"]
-    if p0.meta["n_gops"] == 0:
-        raise ValueError("grouped guided program: no op of the denoiser streams enough weights to be grouped")
-    return p0
+    return _compile_members(lambda m, alias: compile_guided2(net, clf, horizon, max_lds_bytes=max_lds_bytes, member=(m, k), grouped=True,
+                                                             alias_residual=alias, save_global=save_global),
+                            k, True, "grouped guided program: no op of the denoiser")
