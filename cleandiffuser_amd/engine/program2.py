@@ -930,7 +930,7 @@ def chiunet_film_spec(net, blocks, n_emb: int, dev) -> dict:
     return {"w_t": w_t.contiguous(), "w_c": w_c.contiguous(), "bias": bias.contiguous()}
 
 
-def supports_chiunet2(net) -> Optional[str]:
+def unsupported_chiunet2(net) -> Optional[str]:
     if not net.obs_as_global_cond:
         return "local (per-timestep) observation conditioning: implicit-GEMM executor only"
     k = net.final_conv[0].kernel_size[0]
@@ -943,7 +943,7 @@ def compile_chiunet2(net, horizon: int, max_lds_bytes: int = 160 * 1024, allow_4
                      max_stage: Optional[int] = None) -> Program2:
     """Lower a ChiUNet1d with a global condition (reference nn_diffusion/chiunet.py:48-192) for `horizon` positions; same program
     format and kernel as JannerUNet1d.  The FiLM table is filled by the host from ``meta["chi_film"]`` (no embedding MLP spec)."""
-    why = supports_chiunet2(net)
+    why = unsupported_chiunet2(net)
     if why is not None:
         raise ValueError(why)
     b = _unet_builder(net, nw, allow_4x4=allow_4x4, compact=compact, max_stage=max_stage)

@@ -23,7 +23,7 @@ import contextlib
 import functools
 import os
 import threading
-from typing import Optional
+from typing import Callable, NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -35,17 +35,10 @@ def enabled() -> bool:
     return os.environ.get("CDX_TRAIN_NATIVE", "1") != "0"
 
 
-def supports(net, x: torch.Tensor, condition=None) -> bool:
-    """JannerUNet1d (GroupNorm, no attention) with fp32 parameters on a ROCm device, called with autograd on."""
+def _janner_fits(net, x, condition) -> bool:
+    """JannerUNet1d: GroupNorm, no attention, an odd kernel of at most 5 taps."""
     from .consts import supports_janner
-    from .runtime import _is_janner
-    if not (enabled() and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and _is_janner(net)):
-        return False
-    if supports_janner(net) is not None or net.kernel_size > 5:
-        return False
-    if not _groupnorms_ok(net) or not _wants_grad(net, x, condition):
-        return False
-    return all(p.dtype == torch.float32 and p.is_cuda for p in net.parameters())
+    return supports_janner(net) is None and net.kernel_size <= 5 and _groupnorms_ok(net)
 
 
 def _groupnorms_ok(net) -> bool:
@@ -442,46 +435,22 @@ class _ConvT(torch.autograd.Function):
         return dx, dw, db, None, None
 
 
-class _GroupNormMish(torch.autograd.Function):
-    """GroupNorm1d [-> Mish] on channel-last rows (reference utils/building_blocks.py:60-76 + nn.Mish); `act` "mish" (default) or "none"."""
+class _GroupNormAct(torch.autograd.Function):
+    """``act(GroupNorm1d(x)) [+ film[b]] [+ res]`` on channel-last rows in ONE launch forward (reference utils/building_blocks.py:60-76 +
+    nn.Mish; cdx_groupnorm_f32: film_mode 2 and the residual operand); `act` "mish" or "none".  The two adds of a ResidualBlock
+    (reference jannerunet.py:66-69: ``conv1(x) + emb_mlp(emb)``, ``conv2(.) + residual_conv(x)``) were an ATen launch each, 32 of a
+    config-2 step.  Each result element is still one fp32 add per term, as ATen's.  Backward: the additive terms pass dy through
+    (`res`: as it is, no launch; `film`: summed over a sample's positions)."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, batch, length, groups, eps, act="mish"):
+    def forward(ctx, x, gamma, beta, film, res, batch, length, groups, eps, act):
         x = x.contiguous()
-        y = blocks.groupnorm(x, gamma, beta, batch, length, groups, act=act, eps=eps)
-        ctx.save_for_backward(x, gamma, beta)
-        ctx.geom = (batch, length, groups, eps, act)
-        ctx.params = (gamma, beta)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, gamma, beta = ctx.saved_tensors
-        batch, length, groups, eps, act = ctx.geom
-        slots = (_grad_slot(ctx.params[0]), _grad_slot(ctx.params[1])) if ctx.needs_input_grad[1] and ctx.needs_input_grad[2] else (None, None)
-        slots = slots if slots[0] is not None and slots[1] is not None else None
-        dx, dg, db = blocks.groupnorm_backward(dy.contiguous(), x, gamma.detach(), beta.detach(), batch, length, groups, act=act, eps=eps,
-                                               param_grads=True, grads_out=slots)
-        if slots is not None:
-            _written(*slots)
-        return dx, dg, db, None, None, None, None, None
-
-
-class _GroupNormMishAdd(torch.autograd.Function):
-    """``Mish(GroupNorm1d(x)) [+ film[b]] [+ res]`` in ONE launch forward (cdx_groupnorm_f32: film_mode 2 and the residual operand) --
-    the two adds of a ResidualBlock (reference jannerunet.py:66-69: ``conv1(x) + emb_mlp(emb)``, ``conv2(.) + residual_conv(x)``) were
-    an ATen launch each, 32 of a config-2 step.  Each result element is still one fp32 add per term, as ATen's.  Backward: the
-    additive terms pass dy through (`res`: as it is, no launch; `film`: summed over a sample's positions)."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, film, res, batch, length, groups, eps):
-        x = x.contiguous()
-        y = blocks.groupnorm(x, gamma, beta, batch, length, groups, act="mish", eps=eps,
+        y = blocks.groupnorm(x, gamma, beta, batch, length, groups, act=act, eps=eps,
                              fb=None if film is None else (film if film.stride(1) == 1 else film.contiguous()),
                              film_mode=2 if film is not None else 0,
                              residual=None if res is None else res.contiguous())
         ctx.save_for_backward(x, gamma, beta)
-        ctx.geom = (batch, length, groups, eps)
+        ctx.geom = (batch, length, groups, eps, act)
         ctx.params = (gamma, beta)
         ctx.has = (film is not None, res is not None)
         return y
@@ -489,7 +458,7 @@ class _GroupNormMishAdd(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, gamma, beta = ctx.saved_tensors
-        batch, length, groups, eps = ctx.geom
+        batch, length, groups, eps, act = ctx.geom
         dy = dy.contiguous()
         slots = (_grad_slot(ctx.params[0]), _grad_slot(ctx.params[1])) if ctx.needs_input_grad[1] and ctx.needs_input_grad[2] else (None, None)
         slots = slots if slots[0] is not None and slots[1] is not None else None
@@ -499,14 +468,14 @@ class _GroupNormMishAdd(torch.autograd.Function):
         dfilm = None
         if ctx.has[0] and ctx.needs_input_grad[3] and cgw & (cgw - 1) == 0 and cgw <= 256 and os.environ.get("CDX_TRAIN_POSSUM", "1") != "0":
             dfilm = torch.empty((batch, x.shape[1]), device=x.device, dtype=torch.float32)
-        dx, dg, db = blocks.groupnorm_backward(dy, x, gamma.detach(), beta.detach(), batch, length, groups, act="mish", eps=eps,
+        dx, dg, db = blocks.groupnorm_backward(dy, x, gamma.detach(), beta.detach(), batch, length, groups, act=act, eps=eps,
                                                param_grads=True, grads_out=slots, possum_out=dfilm)
         if slots is not None:
             _written(*slots)
         if dfilm is None and ctx.has[0] and ctx.needs_input_grad[3]:
             dfilm = dy.view(batch, length, -1).sum(1)
         dres = dy if ctx.has[1] and ctx.needs_input_grad[4] else None
-        return dx, dg, db, dfilm, dres, None, None, None, None
+        return dx, dg, db, dfilm, dres, None, None, None, None, None
 
 
 class _ConvPair(torch.autograd.Function):
@@ -623,7 +592,7 @@ def _cna(h, seq: nn.Sequential, batch: int, length: int):
     """Conv1d -> GroupNorm1d -> Mish (a `_conv_norm_act` Sequential of nn_diffusion/jannerunet.py)."""
     conv, gn = seq[0], seq[1]
     y = _conv(h, conv, batch, length)
-    return _GroupNormMish.apply(y, gn.weight, gn.bias, batch, length, gn.num_groups, gn.eps)
+    return _GroupNormAct.apply(y, gn.weight, gn.bias, None, None, batch, length, gn.num_groups, gn.eps, "mish")
 
 
 def _resblock(rb, h, memb, batch: int, length: int, film=None):
@@ -633,7 +602,7 @@ def _resblock(rb, h, memb, batch: int, length: int, film=None):
     c_out = rb.conv1[0].out_channels
     lin = rb.emb_mlp[1]
     if film is None:
-        film = _LinearMish.apply(memb, lin.weight, lin.bias, False)                  # (batch, c_out)
+        film = _LinearAct.apply(memb, lin.weight, lin.bias, None)                    # (batch, c_out)
     (conv1, gn1), (conv2, gn2), rc = rb.conv1[:2], rb.conv2[:2], rb.residual_conv
     if os.environ.get("CDX_TRAIN_FUSED_ADDS", "1") == "0":                          # (the round-5 graph: one ATen add per term)
         res = h if isinstance(rc, nn.Identity) else _conv(h, rc, batch, length)
@@ -649,8 +618,8 @@ def _resblock(rb, h, memb, batch: int, length: int, film=None):
     else:
         res = h if isinstance(rc, nn.Identity) else _conv(h, rc, batch, length)
         y1 = _conv(h, conv1, batch, length)
-    a1 = _GroupNormMishAdd.apply(y1, gn1.weight, gn1.bias, film, None, batch, length, gn1.num_groups, gn1.eps)
-    return _GroupNormMishAdd.apply(_conv(a1, conv2, batch, length), gn2.weight, gn2.bias, None, res, batch, length, gn2.num_groups, gn2.eps)
+    a1 = _GroupNormAct.apply(y1, gn1.weight, gn1.bias, film, None, batch, length, gn1.num_groups, gn1.eps, "mish")
+    return _GroupNormAct.apply(_conv(a1, conv2, batch, length), gn2.weight, gn2.bias, None, res, batch, length, gn2.num_groups, gn2.eps, "mish")
 
 
 @_with_weight_packs
@@ -687,15 +656,12 @@ def janner_forward(net, x: torch.Tensor, noise: torch.Tensor, condition: Optiona
     return h.view(b, length, d)
 
 
-def supports_half_janner(net, x: torch.Tensor, condition=None) -> bool:
-    """HalfJannerUNet1d (GroupNorm) with fp32 parameters on a ROCm device, called with autograd on: the classifier's training forward
-    (``CumRewClassifier.update`` / ``update_classifier``, reference classifier/base.py:47-58, diffusionsde.py:143-149)."""
-    from ..nn_classifier.half_jannerunet import HalfJannerUNet1d
-    if not (enabled() and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and type(net) is HalfJannerUNet1d):
-        return False
+def _half_janner_fits(net, x, condition) -> bool:
+    """HalfJannerUNet1d (GroupNorm): the classifier's training forward (``CumRewClassifier.update`` / ``update_classifier``, reference
+    classifier/base.py:47-58, diffusionsde.py:143-149)."""
     if net.norm_type != "groupnorm" or net.kernel_size % 2 == 0 or net.kernel_size > 5 or x.dim() != 3 or x.shape[1] != net.horizon:
         return False
-    if not _groupnorms_ok(net) or not _wants_grad(net, x, condition):
+    if not _groupnorms_ok(net):
         return False
     length = net.horizon                       # the backward of a stride-2 conv is written for even input lengths (short horizons: ATen)
     for down in [d for _, _, d in net.downs] + [net.mid_block1[1], net.mid_block2[1]]:
@@ -703,7 +669,7 @@ def supports_half_janner(net, x: torch.Tensor, condition=None) -> bool:
             if length % 2:
                 return False
             length //= 2
-    return all(p.dtype == torch.float32 and p.is_cuda for p in net.parameters())
+    return True
 
 
 @_with_weight_packs
@@ -731,16 +697,9 @@ def half_janner_forward(net, x: torch.Tensor, noise: torch.Tensor, condition: Op
     return _sequential(net.final_block, torch.cat([flat, raw], dim=-1))
 
 
-def supports_chi(net, x: torch.Tensor, condition=None) -> bool:
-    """ChiUNet1d with a global condition (the dp_* configuration, BASELINE config 3) with fp32 parameters on a ROCm device, called
-    with autograd on."""
-    if not (enabled() and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and type(net).__name__ == "ChiUNet1d"):
-        return False
-    if not net.obs_as_global_cond or condition is None or net.final_conv[0].kernel_size[0] > 5:
-        return False
-    if not _groupnorms_ok(net) or not _wants_grad(net, x, condition):
-        return False
-    return all(p.dtype == torch.float32 and p.is_cuda for p in net.parameters())
+def _chi_fits(net, x, condition) -> bool:
+    """ChiUNet1d with a global condition (the dp_* configuration, BASELINE config 3)."""
+    return bool(net.obs_as_global_cond) and condition is not None and net.final_conv[0].kernel_size[0] <= 5 and _groupnorms_ok(net)
 
 
 def _chi_block(rb, h, memb, batch: int, length: int):
@@ -749,7 +708,7 @@ def _chi_block(rb, h, memb, batch: int, length: int):
     c_out = rb.out_dim
     a1 = _cna(h, rb.conv1, batch, length).view(batch, length, c_out)
     lin = rb.cond_encoder[1]
-    film = _LinearMish.apply(memb, lin.weight, lin.bias, False)
+    film = _LinearAct.apply(memb, lin.weight, lin.bias, None)
     if rb.cond_predict_scale:
         film = film.view(batch, 2, c_out)
         a1 = film[:, 0, None, :] * a1 + film[:, 1, None, :]
@@ -793,38 +752,13 @@ def chi_forward(net, x: torch.Tensor, noise: torch.Tensor, condition: torch.Tens
 
 
 # --------------------------------------------------------------------------------------------------------------------- #
-# Linear (+ Mish) nodes: the MLP denoisers under autograd -- DQL's policy update back-propagates through sample()           #
+# Linear (+ activation) nodes: the MLP denoisers under autograd -- DQL's policy update back-propagates through sample()     #
 # --------------------------------------------------------------------------------------------------------------------- #
-class _LinearMish(torch.autograd.Function):
-    """y = [Mish](x W^T + b) on (batch, features) rows: forward = ``cdx_gemm_f32`` (bias in the epilogue) [+ ``cdx_act_f32``]; backward:
-    dz = dy * Mish'(z) (``cdx_act_bwd_f32``), dx = dz W (the same GEMM on the transposed weight), dW / db = ``cdx_conv_wgrad_f32`` with
-    one tap (a TN GEMM over the batch rows) and its bias column sums."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, mish):
-        x = x.contiguous()
-        z = _linear(x, weight, bias)
-        ctx.mish = mish
-        ctx.params, ctx.packs = (weight, bias), _current_packs()
-        ctx.save_for_backward(x, weight, z if mish else x.new_empty(0))
-        return blocks.activation(z, "mish") if mish else z
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, weight, z = ctx.saved_tensors
-        dz = dy.contiguous()
-        if ctx.mish:
-            dz = blocks.activation_backward(z, dz, "mish")
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = _linear(dz, _pack("linear_t", weight, ctx.packs))
-        dw, db = _weight_grads(dz, x, x.shape[0], 1, 1, 1, 1, 0, ctx.params[0], ctx.params[1], ctx.needs_input_grad[1], ctx.needs_input_grad[2])
-        return dx, dw, db, None
-
-
 class _LinearAct(torch.autograd.Function):
-    """y = act(x W^T + b), act in {None, "mish", "gelu_tanh", ...}: ``cdx_gemm_f32`` with the bias in its epilogue (+ ``cdx_act_f32``
-    when the pre-activation must be kept); backward as ``_LinearMish``."""
+    """y = act(x W^T + b) on (batch, features) rows, act in {None, "mish", "gelu_tanh", ...}: forward = ``cdx_gemm_f32`` (bias in the
+    epilogue) [+ ``cdx_act_f32``: the pre-activation is kept]; backward: dz = dy * act'(z) (``cdx_act_bwd_f32``), dx = dz W (the same
+    GEMM on the transposed weight), dW / db = ``cdx_conv_wgrad_f32`` with one tap (a TN GEMM over the batch rows) and its bias column
+    sums."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, act):
@@ -962,13 +896,9 @@ def draw_keep(p: float, training: bool, batch: int, n_heads: int, tq: int, tk: i
     return torch.empty((batch, n_heads, tq, tk), device=device, dtype=torch.float32).bernoulli_(1.0 - p).mul_(1.0 / (1.0 - p))
 
 
-def supports_idql(net, x: torch.Tensor, condition=None) -> bool:
-    """IDQLMlp / NewIDQLMlp (BASELINE config 5's SynthER residual MLP) with autograd on, on a ROCm device."""
-    if not (enabled() and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2):
-        return False
-    if type(net).__name__ not in ("IDQLMlp", "NewIDQLMlp") or net.affine_in.out_features > 4096 or not _wants_grad(net, x, condition):
-        return False
-    return all(p.dtype == torch.float32 and p.is_cuda for p in net.parameters())
+def _idql_fits(net, x, condition) -> bool:
+    """IDQLMlp / NewIDQLMlp (BASELINE config 5's SynthER residual MLP)."""
+    return x.dim() == 2 and net.affine_in.out_features <= 4096
 
 
 @_with_weight_packs
@@ -987,17 +917,11 @@ def idql_forward(net, x, noise, condition):
     return _LinearAct.apply(h, head.weight, head.bias, None)
 
 
-def supports_dit(net, x: torch.Tensor, condition=None) -> bool:
-    """DiT1d (BASELINE config 4) with autograd on, on a ROCm device: <= 64 tokens, head_dim <= 64."""
-    if not (enabled() and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and
-            type(net).__name__ in ("DiT1d", "HalfDiT1d")):       # (HalfDiT1d: the same trunk with a d_model / 2 wide final layer)
-        return False
-    blk = net.blocks[0] if len(net.blocks) else None
-    if blk is None or x.shape[1] > 64 or net.d_model // blk.attn.num_heads > 64 or net.d_model > 4096 or net.d_model % blk.attn.num_heads:
-        return False
-    if not _wants_grad(net, x, condition):
-        return False
-    return all(p.dtype == torch.float32 and p.is_cuda for p in net.parameters())
+def _dit_fits(net, x, condition) -> bool:
+    """DiT1d (BASELINE config 4) and HalfDiT1d (the same trunk with a d_model / 2 wide final layer): <= 64 tokens, head_dim <= 64."""
+    blk = net.blocks[0] if x.dim() == 3 and len(net.blocks) else None
+    return blk is not None and not (x.shape[1] > 64 or net.d_model // blk.attn.num_heads > 64 or net.d_model > 4096 or
+                                    net.d_model % blk.attn.num_heads)
 
 
 @_with_weight_packs
@@ -1044,15 +968,12 @@ def _tf_layer_ok(layer, d: int, decoder: bool) -> bool:
     return not decoder or _mha_ok(layer.multihead_attn, d)
 
 
-def supports_chitf(net, x: torch.Tensor, condition=None) -> bool:
-    """ChiTransformer (Diffusion Policy's transformer denoiser, the dp_* pipelines) with autograd on, on a ROCm device: the shapes its
-    masks were built for (Ta action tokens, 1 + To memory tokens, both <= 64), head_dim <= 64, pre-norm GELU layers as the class
-    constructs them (reference nn_diffusion/chitransformer.py:90-135)."""
-    if not (enabled() and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and
-            type(net).__name__ == "ChiTransformer"):
-        return False
+def _chitf_fits(net, x, condition) -> bool:
+    """ChiTransformer (Diffusion Policy's transformer denoiser, the dp_* pipelines): the shapes its masks were built for (Ta action
+    tokens, 1 + To memory tokens, both <= 64), head_dim <= 64, pre-norm GELU layers as the class constructs them (reference
+    nn_diffusion/chitransformer.py:90-135)."""
     d = net.act_emb.out_features
-    if x.shape[1] != net.T or net.T > 64 or net.T_cond > 64 or d > 4096 or net.obs_emb is None:
+    if x.dim() != 3 or x.shape[1] != net.T or net.T > 64 or net.T_cond > 64 or d > 4096 or net.obs_emb is None:
         return False
     if condition is not None and not (torch.is_tensor(condition) and condition.dim() == 3 and condition.shape[1] == net.To and
                                       condition.dtype == torch.float32):
@@ -1063,9 +984,7 @@ def supports_chitf(net, x: torch.Tensor, condition=None) -> bool:
             return False
     elif not (isinstance(enc, nn.Sequential) and len(enc) == 3 and isinstance(enc[1], nn.Mish)):
         return False
-    if net.decoder.norm is not None or not all(_tf_layer_ok(l, d, True) for l in net.decoder.layers) or not _wants_grad(net, x, condition):
-        return False
-    return all(p.dtype == torch.float32 and p.is_cuda for p in net.parameters())
+    return net.decoder.norm is None and all(_tf_layer_ok(l, d, True) for l in net.decoder.layers)
 
 
 def _self_attention(att, h2, batch, tokens, mask):
@@ -1119,15 +1038,11 @@ def chitf_forward(net, x, noise, condition):
     return _LinearAct.apply(h, net.head.weight, net.head.bias, None).view(b, ta, net.head.out_features)
 
 
-def supports_mlp(net, x: torch.Tensor, condition=None) -> bool:
-    """DQLMlp / DVInvMlp (Linear -> Mish trunks) with fp32 parameters on a ROCm device, called with autograd on -- what
-    ``sample(..., requires_grad=True)`` of the Diffusion-QL policy update runs at every denoising step (reference
-    pipelines/dql_d4rl_mujoco.py:101, diffusionsde.py:401-427)."""
-    if not (enabled() and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2):
-        return False
-    if type(net).__name__ not in ("DQLMlp", "DVInvMlp") or not _wants_grad(net, x, condition):
-        return False
-    return all(p.dtype == torch.float32 and p.is_cuda for p in net.parameters())
+def _rows_fit(net, x, condition) -> bool:
+    """The MLP denoisers on (batch, features) rows.  DQLMlp / DVInvMlp (Linear -> Mish trunks): what ``sample(..., requires_grad=True)``
+    of the Diffusion-QL policy update runs at every denoising step (reference pipelines/dql_d4rl_mujoco.py:101, diffusionsde.py:401-427);
+    SfBCUNet: the sfbc_* pipelines' residual MLP."""
+    return x.dim() == 2
 
 
 def _sequential(seq: nn.Sequential, h):
@@ -1138,7 +1053,7 @@ def _sequential(seq: nn.Sequential, h):
         m = mods[i]
         if isinstance(m, nn.Linear) and m.bias is not None:
             mish = i + 1 < len(mods) and isinstance(mods[i + 1], nn.Mish)
-            h = _LinearMish.apply(h, m.weight, m.bias, mish)
+            h = _LinearAct.apply(h, m.weight, m.bias, "mish" if mish else None)
             i += 2 if mish else 1
         else:
             h = m(h)
@@ -1226,24 +1141,19 @@ def dql_forward(net, x: torch.Tensor, noise: torch.Tensor, condition: Optional[t
     temb = _sequential(net.time_mlp, net.map_noise(noise).contiguous())
     h = torch.cat([x, temb, condition], -1)
     h = _sequential(net.mid_layer, h)
-    return _LinearMish.apply(h, net.final_layer.weight, net.final_layer.bias, False)
+    return _LinearAct.apply(h, net.final_layer.weight, net.final_layer.bias, None)
 
 
-def supports_pearce(net, x: torch.Tensor, condition=None) -> bool:
-    """PearceMlp (BASELINE config 1, the dbc_* pipelines) with autograd on, on a ROCm device."""
-    if not (enabled() and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and
-            type(net).__name__ == "PearceMlp"):
-        return False
-    if not _groupnorms_ok(net) or not _wants_grad(net, x, condition):
-        return False
-    return all(p.dtype == torch.float32 and p.is_cuda for p in net.parameters())
+def _pearce_fits(net, x, condition) -> bool:
+    """PearceMlp (BASELINE config 1, the dbc_* pipelines)."""
+    return x.dim() == 2 and _groupnorms_ok(net)
 
 
 def _fc_block(block, h):
     """FCBlock (reference nn_diffusion/pearcemlp.py:10-23): Linear -> GroupNorm1d over the features of one row -> GELU(erf)."""
     lin, gn, _ = block.model
     z = _LinearAct.apply(h, lin.weight, lin.bias, None)
-    z = _GroupNormMish.apply(z, gn.weight, gn.bias, z.shape[0], 1, gn.num_groups, gn.eps, "none")
+    z = _GroupNormAct.apply(z, gn.weight, gn.bias, None, None, z.shape[0], 1, gn.num_groups, gn.eps, "none")
     return _Act.apply(z, "gelu")
 
 
@@ -1262,14 +1172,6 @@ def pearce_forward(net, x, noise, condition):
         h = _fc_block(block, torch.cat([skip, x, t], -1)) + skip
     last = net.fcs[3]
     return _LinearAct.apply(torch.cat([h, x, t], -1), last.weight, last.bias, None)
-
-
-def supports_sfbc(net, x: torch.Tensor, condition=None) -> bool:
-    """SfBCUNet (the sfbc_* pipelines' residual MLP) with autograd on, on a ROCm device."""
-    if not (enabled() and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and
-            type(net).__name__ == "SfBCUNet") or not _wants_grad(net, x, condition):
-        return False
-    return all(p.dtype == torch.float32 and p.is_cuda for p in net.parameters())
 
 
 def _sfbc_block(rb, h, c):
@@ -1295,6 +1197,66 @@ def sfbc_forward(net, x, noise, condition):
     for block in net.up_blocks:
         x = _sfbc_block(block, torch.cat([x, kept.pop()], dim=-1), c)
     return _LinearAct.apply(x, net.out_layer.weight, net.out_layer.bias, None)
+
+
+# --------------------------------------------------------------------------------------------------------------------- #
+# The families: which nets this path takes, and with which forward                                                              #
+# --------------------------------------------------------------------------------------------------------------------- #
+class Family(NamedTuple):
+    name: str
+    belongs: Callable          # class -> bool: how the family knows its nets
+    fits: Callable             # (net, x, condition) -> bool: the family's own shapes and structure (asked of its own classes only)
+    forward: str               # the name of its forward in this module (looked up per call: tests and users patch it)
+    role: str                  # "denoiser" (update() through graphed_step) | "classifier" (graphed_classifier_step)
+
+
+def _named(*names):                                        # (the class's name, exactly: a subclass is another net)
+    return lambda cls: cls.__name__ in names
+
+
+def _janner_class(cls) -> bool:                            # (subclasses count)
+    from ..nn_diffusion.jannerunet import JannerUNet1d
+    return issubclass(cls, JannerUNet1d)
+
+
+def _half_janner_class(cls) -> bool:
+    from ..nn_classifier.half_jannerunet import HalfJannerUNet1d
+    return cls is HalfJannerUNet1d
+
+
+FAMILIES = (
+    Family("janner", _janner_class, _janner_fits, "janner_forward", "denoiser"),
+    Family("half_janner", _half_janner_class, _half_janner_fits, "half_janner_forward", "classifier"),
+    Family("chi", _named("ChiUNet1d"), _chi_fits, "chi_forward", "denoiser"),
+    Family("dit", _named("DiT1d", "HalfDiT1d"), _dit_fits, "dit_forward", "denoiser"),
+    Family("chitf", _named("ChiTransformer"), _chitf_fits, "chitf_forward", "denoiser"),
+    Family("idql", _named("IDQLMlp", "NewIDQLMlp"), _idql_fits, "idql_forward", "denoiser"),
+    Family("mlp", _named("DQLMlp", "DVInvMlp"), _rows_fit, "dql_forward", "denoiser"),
+    Family("pearce", _named("PearceMlp"), _pearce_fits, "pearce_forward", "denoiser"),
+    Family("sfbc", _named("SfBCUNet"), _rows_fit, "sfbc_forward", "denoiser"),
+)
+_family_of_class: dict = {}     # class -> its row or None, filled the first time a class asks (a forward() pays one lookup, not a scan)
+
+
+def family_of(net, x: torch.Tensor, condition=None) -> Optional[Family]:
+    """The family that takes ``net(x, noise, condition)``, or None: a net of one of its classes that fits, called with autograd on and
+    something to differentiate, fp32 input and parameters on a ROCm device."""
+    cls = type(net)
+    try:
+        fam = _family_of_class[cls]
+    except KeyError:
+        fam = _family_of_class[cls] = next((f for f in FAMILIES if f.belongs(cls)), None)
+    if fam is None or not (enabled() and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32):
+        return None
+    if not fam.fits(net, x, condition) or not _wants_grad(net, x, condition):
+        return None
+    return fam if all(p.dtype == torch.float32 and p.is_cuda for p in net.parameters()) else None
+
+
+def forward(net, x: torch.Tensor, noise: torch.Tensor, condition=None) -> Optional[torch.Tensor]:
+    """``net(x, noise, condition)`` on the library's nodes, or None: no family takes the call (the module goes on with its other paths)."""
+    fam = family_of(net, x, condition)
+    return None if fam is None else globals()[fam.forward](net, x, noise, condition)
 
 
 # --------------------------------------------------------------------------------------------------------------------- #
@@ -1426,48 +1388,52 @@ class GraphedStep:
         return self.loss
 
 
-def _native_training_net(net, x0, condition) -> bool:
+def _cached_step(owner, eligible, key, capture) -> Optional[GraphedStep]:
+    """The GraphedStep `owner` (an agent, a classifier) keeps under `key`, captured by ``capture()`` when there is none -- or None: the
+    eager path (``eligible()`` says no, an earlier capture failed, too many shapes, tensors that keep moving)."""
+    if owner.__dict__.get("_cdx_graph_off") or not eligible():
+        return None
+    cache = owner.__dict__.setdefault("_cdx_graphed", {})
+    g = cache.get(key)
+    if g is not None and not g.valid():
+        # captured on tensors that are gone: capture again -- unless that keeps happening (an optimiser that drops the gradients after
+        # every step): then the eager path serves this owner
+        owner._cdx_recaptures = getattr(owner, "_cdx_recaptures", 0) + 1
+        g = cache[key] = None
+    if getattr(owner, "_cdx_recaptures", 0) > RECAPTURE_LIMIT:
+        return None
+    if g is None:
+        if key not in cache and len(cache) >= SHAPE_LIMIT:
+            return None                                # (a loop over ever-changing batch shapes: capturing each would cost more than it saves)
+        try:
+            g = cache[key] = capture()
+        except NotCapturable as e:
+            owner.__dict__["_cdx_graph_off"] = str(e)  # (kept for diagnostics: why this owner steps eagerly)
+            cache.pop(key, None)
+            return None
+    return g
+
+
+def _native_training_net(net, x0, condition, role: str = "denoiser") -> bool:
     with torch.enable_grad():
-        return (supports(net, x0, condition) or supports_chi(net, x0, condition) or supports_dit(net, x0, condition) or
-                supports_chitf(net, x0, condition) or supports_idql(net, x0, condition) or supports_mlp(net, x0, condition) or
-                supports_pearce(net, x0, condition) or supports_sfbc(net, x0, condition))
+        fam = family_of(net, x0, condition)
+    return fam is not None and fam.role == role
 
 
 def graphed_step(agent, x0, condition, kwargs) -> Optional[GraphedStep]:
     """The cached GraphedStep of (agent, batch shape), or None (the eager path).  CDX_TRAIN_GRAPH: "auto" (default) -- agents whose
-    denoiser the native training path serves (JannerUNet1d, ChiUNet1d, DiT1d, ChiTransformer, IDQLMlp, PearceMlp, SfBCUNet, DQLMlp / DVInvMlp on a ROCm device), no extra
-    loss arguments, and whose first step passes the capturability probe (GraphedStep); "1": no probe; "0": never."""
+    denoiser the native training path serves (the "denoiser" rows of FAMILIES, on a ROCm device), no extra loss arguments, and whose
+    first step passes the capturability probe (GraphedStep); "1": no probe; "0": never."""
     mode = os.environ.get("CDX_TRAIN_GRAPH", "auto")
     if mode == "0" or kwargs or not torch.is_tensor(x0) or not x0.is_cuda or not torch.is_grad_enabled() or \
             torch.cuda.is_current_stream_capturing():
         return None
     if condition is not None and not (torch.is_tensor(condition) and condition.device == x0.device):
         return None                                        # (dictionaries of observations, host tensors: not a static buffer -- eager)
-    if agent.__dict__.get("_cdx_graph_off"):
-        return None
-    net = agent.model["diffusion"]
-    if not _native_training_net(net, x0, condition):       # (the raw condition stands in for the encoded one: only its presence matters)
-        return None
-    key = (tuple(x0.shape), None if condition is None else tuple(condition.shape), agent.model.training)
-    cache = agent.__dict__.setdefault("_cdx_graphed", {})
-    g = cache.get(key)
-    if g is not None and not g.valid():
-        # captured on tensors that are gone: capture again -- unless that keeps happening (an optimiser that drops the gradients after
-        # every step): then the eager path serves this agent
-        agent._cdx_recaptures = getattr(agent, "_cdx_recaptures", 0) + 1
-        g = cache[key] = None
-    if getattr(agent, "_cdx_recaptures", 0) > RECAPTURE_LIMIT:
-        return None
-    if g is None:
-        if key not in cache and len(cache) >= SHAPE_LIMIT:
-            return None                                # (a loop over ever-changing batch shapes: capturing each would cost more than it saves)
-        try:
-            g = cache[key] = GraphedStep(agent, x0, condition, probe=(mode != "1"))
-        except NotCapturable as e:
-            agent.__dict__["_cdx_graph_off"] = str(e)  # (kept for diagnostics: why this agent steps eagerly)
-            cache.pop(key, None)
-            return None
-    return g
+    # (the raw condition stands in for the encoded one: only its presence matters)
+    return _cached_step(agent, lambda: _native_training_net(agent.model["diffusion"], x0, condition),
+                        (tuple(x0.shape), None if condition is None else tuple(condition.shape), agent.model.training),
+                        lambda: GraphedStep(agent, x0, condition, probe=(mode != "1")))
 
 
 class _ClassifierStep:
@@ -1482,29 +1448,13 @@ class _ClassifierStep:
 
 def graphed_classifier_step(clf, x, noise, y) -> Optional[GraphedStep]:
     """The cached GraphedStep of a classifier's ``loss(x, noise, y); backward()`` (``BaseClassifier.update``), or None (the eager pair):
-    same rules as `graphed_step` -- a HalfJannerUNet1d on a ROCm device, tensors for all three inputs, a first step that passes the
-    capturability probe (CDX_TRAIN_GRAPH: "auto" / "1" / "0")."""
+    same rules as `graphed_step` -- a trunk of the "classifier" family on a ROCm device, tensors for all three inputs, a first step that
+    passes the capturability probe (CDX_TRAIN_GRAPH: "auto" / "1" / "0")."""
     mode = os.environ.get("CDX_TRAIN_GRAPH", "auto")
     if mode == "0" or not all(torch.is_tensor(t) and t.is_cuda and t.device == x.device for t in (x, noise, y)) or \
-            not torch.is_grad_enabled() or torch.cuda.is_current_stream_capturing() or clf.__dict__.get("_cdx_graph_off"):
+            not torch.is_grad_enabled() or torch.cuda.is_current_stream_capturing():
         return None
-    if not supports_half_janner(clf.model, x, None):
-        return None
-    key = (tuple(x.shape), tuple(noise.shape), noise.dtype, tuple(y.shape), clf.model.training)
-    cache = clf.__dict__.setdefault("_cdx_graphed", {})
-    g = cache.get(key)
-    if g is not None and not g.valid():
-        clf._cdx_recaptures = getattr(clf, "_cdx_recaptures", 0) + 1
-        g = cache[key] = None
-    if getattr(clf, "_cdx_recaptures", 0) > RECAPTURE_LIMIT:
-        return None
-    if g is None:
-        if key not in cache and len(cache) >= SHAPE_LIMIT:
-            return None
-        try:
-            g = cache[key] = GraphedStep(_ClassifierStep(clf), x, (noise, y), probe=(mode != "1"))
-        except NotCapturable as e:
-            clf.__dict__["_cdx_graph_off"] = str(e)
-            cache.pop(key, None)
-            return None
-    return g
+    # (no condition, whatever the caller's loss passes on: only the trunk and the batch decide)
+    return _cached_step(clf, lambda: _native_training_net(clf.model, x, None, "classifier"),
+                        (tuple(x.shape), tuple(noise.shape), noise.dtype, tuple(y.shape), clf.model.training),
+                        lambda: GraphedStep(_ClassifierStep(clf), x, (noise, y), probe=(mode != "1")))

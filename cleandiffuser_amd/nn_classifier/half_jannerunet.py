@@ -64,8 +64,9 @@ class HalfJannerUNet1d(BaseNNDiffusion):
 
     def forward(self, x: torch.Tensor, noise: torch.Tensor, condition: Optional[torch.Tensor] = None):
         from ..engine import dispatch, train
-        if train.supports_half_janner(self, x, condition):
-            # autograd on, ROCm device (the classifier's loss() / update()): the same graph on the library's conv / GroupNorm / Linear nodes
-            return train.half_janner_forward(self, x, noise, condition)
+        # autograd on, ROCm device (the classifier's loss() / update()): the same graph on the library's conv / GroupNorm / Linear nodes
+        y = train.forward(self, x, noise, condition)
+        if y is not None:
+            return y
         y = dispatch.try_backbone_forward(self, x, noise, condition)
         return y if y is not None else self._forward_torch(x, noise, condition)

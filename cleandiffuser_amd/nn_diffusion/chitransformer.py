@@ -89,8 +89,9 @@ class ChiTransformer(BaseNNDiffusion):
     def forward(self, x: torch.Tensor, noise: torch.Tensor, condition: Optional[torch.Tensor] = None):
         """x (b, Ta, act_dim), noise (b,), condition (b, To, obs_dim)|None(=zeros) -> (b, Ta, act_dim)."""
         from ..engine import dispatch, train
-        if train.supports_chitf(self, x, condition):
-            return train.chitf_forward(self, x, noise, condition)           # autograd on, ROCm device: loss() / update()
+        y = train.forward(self, x, noise, condition)                        # autograd on, ROCm device: loss() / update()
+        if y is not None:
+            return y
         y = dispatch.try_backbone_forward(self, x, noise, condition)        # cdx_chitf_run on a ROCm device
         if y is not None:
             return y

@@ -176,10 +176,11 @@ class JannerUNet1d(BaseNNDiffusion):
         """x (b, horizon, in_dim), noise (b,), condition (b, emb_dim)|None -> (b, horizon, in_dim)."""
         assert x.shape[1] & (x.shape[1] - 1) == 0, "Ta dimension must be 2^n"
         from ..engine import dispatch, train
-        if train.supports(self, x, condition):
-            # autograd on, ROCm device (loss() / update(), sampling with requires_grad=True): the same graph, every convolution and
-            # GroupNorm node on the library's kernels forward and backward (engine/train.py; SURVEY 8(f4))
-            return train.janner_forward(self, x, noise, condition)
+        # autograd on, ROCm device (loss() / update(), sampling with requires_grad=True): the same graph, every convolution and
+        # GroupNorm node on the library's kernels forward and backward (engine/train.py; SURVEY 8(f4))
+        y = train.forward(self, x, noise, condition)
+        if y is not None:
+            return y
         y = dispatch.try_backbone_forward(self, x, noise, condition)
         if y is not None:
             return y

@@ -57,8 +57,9 @@ class PearceMlp(BaseNNDiffusion):
     def forward(self, x: torch.Tensor, noise: torch.Tensor, condition: Optional[torch.Tensor] = None):
         """x (b, act_dim), noise (b,), condition (b, To, emb_dim) | (b, To*emb_dim) | None -> (b, act_dim)."""
         from ..engine import train
-        if train.supports_pearce(self, x, condition):
-            return train.pearce_forward(self, x, noise, condition)          # autograd on, ROCm device: loss() / update()
+        y = train.forward(self, x, noise, condition)                        # autograd on, ROCm device: loss() / update()
+        if y is not None:
+            return y
         if condition is None:
             condition = torch.zeros(x.shape[0], self.To, self.emb_dim).to(x.device)
         t = noise.unsqueeze(-1)
@@ -97,8 +98,9 @@ class DQLMlp(_ObsConditionedMlp):
 
     def forward(self, x: torch.Tensor, noise: torch.Tensor, condition: Optional[torch.Tensor] = None):
         from ..engine import train
-        if train.supports_mlp(self, x, condition):       # autograd on, ROCm device (DQL back-propagates through sample()): Linear / Mish nodes on the library
-            return train.dql_forward(self, x, noise, condition)
+        y = train.forward(self, x, noise, condition)     # autograd on, ROCm device (DQL back-propagates through sample()): Linear / Mish nodes on the library
+        if y is not None:
+            return y
         return self.final_layer(self.mid_layer(self._features(x, noise, condition)))
 
 
@@ -120,8 +122,9 @@ class DVInvMlp(_ObsConditionedMlp):
         if condition is None:
             raise TypeError("DVInvMlp needs the (obs, next_obs) condition")       # reference: torch.cat fails on None
         from ..engine import train
-        if train.supports_mlp(self, x, condition):
-            return train.dql_forward(self, x, noise, condition)
+        y = train.forward(self, x, noise, condition)
+        if y is not None:
+            return y
         return self.final_layer(self.mid_layer(self._features(x, noise, condition)))
 
 
@@ -154,8 +157,9 @@ class IDQLMlp(_ObsConditionedMlp):
 
     def forward(self, x: torch.Tensor, noise: torch.Tensor, condition: Optional[torch.Tensor] = None):
         from ..engine import dispatch, train
-        if train.supports_idql(self, x, condition):   # autograd on, ROCm device (loss() / update()): Linear / LayerNorm nodes on the library
-            return train.idql_forward(self, x, noise, condition)
+        y = train.forward(self, x, noise, condition)  # autograd on, ROCm device (loss() / update()): Linear / LayerNorm nodes on the library
+        if y is not None:
+            return y
         y = dispatch.try_backbone_forward(self, x, noise, condition)         # cdx_resmlp_run on a ROCm device
         if y is not None:
             return y

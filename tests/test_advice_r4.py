@@ -69,7 +69,7 @@ def test_a_slot_that_goes_from_none_to_a_tensor_enters_the_signature():
 
 
 def test_native_training_graph_is_not_taken_for_shapes_its_groupnorm_backward_cannot_serve(monkeypatch):
-    """train.supports(): GroupNorm groups of 6 / 12 channels (model_dim 48) or of more than 256 channels have no library backward for the gain / shift
+    """train.family_of(): GroupNorm groups of 6 / 12 channels (model_dim 48) or of more than 256 channels have no library backward for the gain / shift
     gradients -- such nets keep the ATen autograd path instead of raising inside loss.backward(); a frozen net on inputs that need no
     gradient is not a training forward at all.  (Device checks are stubbed: this is the host-side rule.)"""
     from cleandiffuser_amd.nn_diffusion import JannerUNet1d
@@ -82,13 +82,13 @@ def test_native_training_graph_is_not_taken_for_shapes_its_groupnorm_backward_ca
             monkeypatch.setattr(type(p), "is_cuda", property(lambda self: True), raising=False)
         return net
     ok = as_cuda(JannerUNet1d(23, model_dim=32, emb_dim=32, dim_mult=[1, 2, 2, 2], timestep_emb_type="positional", attention=False, kernel_size=5))
-    assert train.supports(ok, FakeX())
+    assert train.family_of(ok, FakeX()).name == "janner"
     odd = JannerUNet1d(23, model_dim=48, emb_dim=32, dim_mult=[1, 2], timestep_emb_type="positional", attention=False, kernel_size=5)
-    assert not train.supports(odd, FakeX())
+    assert train.family_of(odd, FakeX()) is None
     # (round 5: groups of up to 256 channels have a library backward -- ChiUNet1d's 1024 / 2048-channel levels; 512 do not)
     assert train._groupnorms_ok(torch.nn.Sequential(torch.nn.GroupNorm(8, 1024), torch.nn.GroupNorm(8, 2048)))
     assert not train._groupnorms_ok(torch.nn.Sequential(torch.nn.GroupNorm(8, 4096)))
     ok.requires_grad_(False)
-    assert not train.supports(ok, FakeX())            # frozen net, input without requires_grad: the fused forward's business
+    assert train.family_of(ok, FakeX()) is None        # frozen net, input without requires_grad: the fused forward's business
     FakeX.requires_grad = True
-    assert train.supports(ok, FakeX())
+    assert train.family_of(ok, FakeX()).name == "janner"

@@ -1,6 +1,6 @@
 """Plain-torch stand-ins for the kernel wrappers of cleandiffuser_amd/engine/blocks.py -- TEST HELPER for the CPU tier.
 
-The training path (engine/train.py) is ~900 lines of HOST logic around the HIP kernels: which node runs which launch with which layout,
+The training path (engine/train.py) is ~1400 lines of HOST logic around the HIP kernels: which node runs which launch with which layout,
 how gradients are routed (autograd, or straight into ``.grad``), when the weight layouts are refreshed.  None of it can execute without a
 GPU -- unless the dozen kernel wrappers it calls are replaced by torch expressions of the same contracts, which is what ``emulated()``
 does (monkeypatch-style, restored on exit).  The KERNELS are checked on the MI355X (tests/test_gpu_parity.py); this checks everything
