@@ -13,7 +13,10 @@ Architecture (different from the reference on purpose):
      one workgroup per trajectory and all activations in LDS.  Chosen when the solver lives on a ROCm device,
      gradients are off, the backbone is one the engine can compile, and no per-step classifier guidance is asked.
    * **PyTorch executor** (``_run_plan_torch`` below): step-by-step, calling ``model["diffusion"]`` like the
-     reference does.  Serves CPU, autograd (``requires_grad=True``, DQL), classifier guidance and user backbones.
+     reference does.  Serves CPU, autograd (``requires_grad=True``) of everything but the row-MLP denoisers, classifier guidance and
+     user backbones.
+   * **differentiable rollout** (engine/rollout.py -> ``cdx_rollout_fwd_f32`` / ``cdx_rollout_bwd_f32``): ``requires_grad=True`` over
+     DQLMlp / DVInvMlp (Diffusion-QL's policy update) -- the loop in one forward and one backward launch.
 3. Noise is drawn in exactly the reference's order (initial draw, then one draw per stochastic step) so a CPU run
    with the same torch seed reproduces the reference; ``noise=[z0, z1, ...]`` (kwarg) replays recorded draws,
    which is how device runs are compared with the CPU oracle and how multi-GPU shards stay seed-consistent.
@@ -270,6 +273,9 @@ class BaseDiffusionSDE(DiffusionModel):
         if not preserve_history:
             fused = dispatch.try_fused_sample(self, model, plan, xt, prior, cond_vec, w_cfg, w_cg,
                                               requires_grad, feed)
+            if fused is None and requires_grad:       # DQL's policy update: the differentiable loop in two launches (engine/rollout.py)
+                from ..engine import rollout
+                fused = rollout.try_rollout(self, model, plan, xt, prior, cond_vec, w_cfg, w_cg, feed)
         if fused is not None:
             xt = fused
         else:

@@ -18,7 +18,7 @@
 extern "C" {
 #endif
 
-#define CDX_ABI_VERSION 17
+#define CDX_ABI_VERSION 18
 
 #define CDX_OK 0
 #define CDX_EINVAL (-1)   /* bad argument (null pointer, size out of range, misaligned offset) */
@@ -730,6 +730,49 @@ typedef struct cdx_resmlp_weights {
 } cdx_resmlp_weights;
 long long cdx_resmlp_workspace_floats(const cdx_resmlp_weights* w, const cdx_sampling* s);
 int cdx_resmlp_run(const cdx_resmlp_weights* w, const cdx_sampling* s, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Differentiable rollout of the row-MLP denoisers (ABI 18; csrc/cdx_rollout.hip): ``sample(..., requires_grad=True)`` of DQLMlp /
+ * DVInvMlp (reference pipelines/dql_d4rl_mujoco.py:98-101 over diffusion/diffusionsde.py:526-594, nn_diffusion/dqlmlp.py:30-52) as ONE
+ * forward launch over all S denoising steps and ONE backward launch over them in reverse.  The net: feat = [x_s (A) | temb_s (E) |
+ * cond (O)] -> 3 x (Linear(., W) -> Mish) -> Linear(W, A); then clip, eps <-> x0, the affine update of the step record (kinds 0 / 1 / 2,
+ * vsel 0 / 1, arithmetic of the big-batch solver step), `+ k z` and the fix-mask blend.  One workgroup owns 16 rows for the whole loop.
+ * Forward saves, backward reads (caller-owned, nothing is allocated here):
+ *   X (S+1, B, A) states, X[0] = x_in, X[S] = the result;  P_raw (S, B, A) head output before the clip;  feat (S, B, A+E+O);
+ *   Z, H (3, S, B, W) pre-activations and Mish(Z) of the hidden layers, LAYER-major: the S*B rows of a layer are one row-major matrix.
+ * Backward writes G = d loss / d Z over Z (in place), G_head (S, B, A) = d loss / d P_raw, g_x (B, A; optional) = d loss / d x_in,
+ * g_cond (B, O; optional, needs cond) summed over the steps, g_temb (B, S*E): d loss / d temb[s][e] of row b at [b][s*E + e] -- one
+ * cdx_colsum_f32 over the B rows gives (S, E).  No atomics: bit-reproducible.  The weight / bias gradients are the caller's:
+ * dW_l = sum_s G[l][s]^T H[l-1][s] is one cdx_conv_wgrad_f32 product (taps 1) per layer over the S*B rows (layer 1: q = feat; head:
+ * p = G_head, q = H[2]).  Through the clamp dP/dP_raw is 1 inside the bounds, 0 outside; with eps-prediction a clamped element hands its
+ * gradient to x_s with the factor 1 / sigma (the bound is a function of x_s).
+ * Limits (CDX_EINVAL): W % 16 == 0, W <= 512, A + E + O <= 512, A <= 64, 1 <= S <= CDX_ROLLOUT_MAX_STEPS, kinds 0-2, vsel <= 1, no flags.
+ * B == 0 is CDX_OK.  Both calls enqueue one kernel on `hip_stream`, never synchronise and are capturable as they stand.
+ * ---------------------------------------------------------------------------------------------- */
+#define CDX_ROLLOUT_MAX_STEPS 64
+typedef struct cdx_rollout {
+    int32_t B, A, E, O, W, S;
+    int32_t predict_noise;     /* the head predicts eps (1) or x0 (0) */
+    int32_t clip;              /* 0: x_min / x_max are ignored inside the loop (plans without per-step clipping) */
+    const float *w1, *b1;      /* (W, A+E+O), (W) */
+    const float *w2, *b2;      /* (W, W), (W) */
+    const float *w3, *b3;      /* (W, W), (W) */
+    const float *wh, *bh;      /* (A, W), (A) */
+    const float* temb;         /* (S, E): time_mlp(map_noise(t_s)), one row per step record */
+    const float* cond;         /* (B, O) or NULL: zeros, and no g_cond */
+    const float* x_in;         /* (B, A) */
+    const float* prior;        /* (B, A) or NULL */
+    const float* fix_mask;     /* (A) or NULL */
+    const float* x_min;        /* (A) or NULL */
+    const float* x_max;        /* (A) or NULL */
+    const float* noise;        /* [n_noise][B][A] or NULL */
+    const cdx_step* steps;     /* HOST [S] */
+    float *X, *P_raw, *feat, *Z, *H;              /* saved by forward (see above) */
+    const float* g_out;        /* backward: (B, A) d loss / d X[S] */
+    float *G_head, *g_x, *g_cond, *g_temb;        /* written by backward */
+} cdx_rollout;
+int cdx_rollout_fwd_f32(const cdx_rollout* r, void* hip_stream);
+int cdx_rollout_bwd_f32(const cdx_rollout* r, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Optimiser side of DiffusionModel.update(): multi-tensor AdamW + EMA + gradient-norm clipping.
