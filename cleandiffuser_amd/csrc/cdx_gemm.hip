@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "../../include/cdx.h"
+#include "cdx_act.h"
 #include "cdx_ops2.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -31,56 +32,23 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define GM_BK 16
 #define GM_LD (GM_BM + 4)
 #define GM_THREADS 256
-#ifndef GM_STAGE_AT
-#define GM_STAGE_AT (BK - 4)                   // k pair of the first half behind which tile t + 1 is parked in LDS (A/B builds)
-#endif
-#ifndef CDX_GEMM_W8_BK
-#define CDX_GEMM_W8_BK 16                      // K tile of the 8-wave shape: 16 (block sums over two tiles) or 32 (one tile = one block; dynamic LDS)
-#endif
-#ifndef CDX_GEMM_W8_DEFAULT
-#define CDX_GEMM_W8_DEFAULT 1               // the 8-wave shape of the 128 x 128 tile by default (same-box A/B: profiles/r05_gemm_w8_ab.txt)
-#endif
-#ifndef CDX_GEMM_PERSIST
-#define CDX_GEMM_PERSIST 0                    // 1: the 8-wave kernel walks several tiles per workgroup (grid = resident slots), the next tile's first
-#endif                                        //    K tile requested before the epilogue of the current one (A/B builds; round 6)
-#ifndef CDX_GEMM_KBLOCK
-#define CDX_GEMM_KBLOCK 1                     // 0: one sequential fma chain over K per element (rounds 1-4; A/B builds)
-#endif
 
 extern void cdx_set_err(const char* msg);
 
 __device__ __forceinline__ float gm_act(float x, int act) {
     switch (act) {
-        case CDX_ACT_MISH: {
-            const float e = __expf(fminf(x, 20.0f));
-            const float n = e * (e + 2.0f);
+        case CDX_ACT_MISH: {                             // cdx_act_mish written out: through the call hipcc lays out every kernel that
+            const float e = __expf(fminf(x, 20.0f));     // inlines this switch differently (same arithmetic, other branch structure), and
+            const float n = e * (e + 2.0f);              // those kernels are tuned as they are
             return x > 20.0f ? x : x * n * __builtin_amdgcn_rcpf(n + 2.0f);
         }
-        case CDX_ACT_GELU_ERF: {                         // exact GELU; erf by Abramowitz-Stegun 7.1.26 (|err| < 1.5e-7, branch-free:
-            const float z = fabsf(x) * 0.70710678118654752f;   // libm erff costs ~4x as much in a GEMM epilogue)
-            const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
-            const float poly = t * fmaf(t, fmaf(t, fmaf(t, fmaf(t, 1.061405429f, -1.453152027f), 1.421413741f), -0.284496736f), 0.254829592f);
-            const float erf_abs = 1.0f - poly * __expf(-z * z);
-            return 0.5f * x * (1.0f + copysignf(erf_abs, x));
-        }
-        case CDX_ACT_LEAKY: return x > 0.f ? x : 0.01f * x;
-        case CDX_ACT_SILU: return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x));
-        case CDX_ACT_RELU: return fmaxf(x, 0.f);
-        case CDX_ACT_MISH_GRAD: {                        // d/dx [x tanh(softplus x)] = t + x (1 - t^2) sigmoid(x)
-            const float e = __expf(fminf(x, 20.0f));
-            const float n = e * (e + 2.0f);
-            const float t = x > 20.0f ? 1.0f : n / (n + 2.0f);
-            const float sg = e / (1.0f + e);
-            return t + x * (1.0f - t * t) * sg;
-        }
-        case CDX_ACT_GELU_TANH: {                        // 0.5 x (1 + tanh u) == x * sigmoid(2u): one v_exp, one v_rcp, no branches
-            const float u2 = 1.5957691216057308f * (x + 0.044715f * x * x * x);
-            return x * __builtin_amdgcn_rcpf(1.0f + __expf(-u2));
-        }
-        case CDX_ACT_TANH: {                             // sign(x) (1 - e^{-2|x|}) / (1 + e^{-2|x|}): no overflow, no branches
-            const float t = __expf(-2.0f * fabsf(x));
-            return copysignf((1.0f - t) * __builtin_amdgcn_rcpf(1.0f + t), x);
-        }
+        case CDX_ACT_GELU_ERF: return cdx_act_gelu_erf(x);
+        case CDX_ACT_LEAKY: return cdx_act_leaky(x);
+        case CDX_ACT_SILU: return cdx_act_silu(x);
+        case CDX_ACT_RELU: return cdx_act_relu(x);
+        case CDX_ACT_MISH_GRAD: return cdx_act_mish_grad(x);
+        case CDX_ACT_GELU_TANH: return cdx_act_gelu_tanh(x);
+        case CDX_ACT_TANH: return cdx_act_tanh(x);
         default: return x;
     }
 }
@@ -261,7 +229,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : (WT == 2 ? 3 : 4))) void cd
     constexpr int THREADS = 64 * NW;
     constexpr int WTM = WT, WTN = NW == 8 ? 1 : WT;      // 32 x 32 blocks per wave (rows x columns)
     constexpr int BMN = 64 * WT;                  // rows of A == rows of W per tile
-    constexpr int BK = NW == 8 ? CDX_GEMM_W8_BK : (WT == 2 ? 16 : 32);          // K tile
+    constexpr int BK = WT == 2 ? 16 : 32;          // K tile (the 8-wave shape: 16, its block sums run over two tiles)
     // Global -> LDS staging map (round 4): a wave's load covers FEW rows in FULL 64 / 128-byte runs -- thread -> (row r0 + i * RPI, k
     // quad q): 16 rows x 64 B per load instruction (128 x 128 tile), 8 rows x 128 B (64 x 64) -- instead of 64 rows x 16 B: a quarter /
     // an eighth of the cache lines per instruction through the CU's memory pipe, which is what the co-resident workgroups' epilogue
@@ -273,23 +241,18 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : (WT == 2 ? 3 : 4))) void cd
     constexpr int LD = WT == 2 ? BMN + 2 : BMN + 1;
     // one LDS arena: two stages of A/B staging tiles [k][row] during the K loop, then NW wave-private 32 x 36 transposition patches
     constexpr int SMEM_FLOATS = (4 * BK * LD > NW * 32 * GM_EP_LD) ? 4 * BK * LD : NW * 32 * GM_EP_LD;
-#if CDX_GEMM_W8_BK == 32
-    // (66.5 KB for the 8-wave shape with 32-wide K tiles: past the 64 KB of static LDS -- dynamic, requested by the launcher)
-    extern __shared__ __attribute__((aligned(16))) float dyn_smem[];
-    __shared__ __attribute__((aligned(16))) float sta_smem[NW == 8 ? 4 : SMEM_FLOATS];
-    float* smem = NW == 8 ? dyn_smem : sta_smem;
-#else
     __shared__ __attribute__((aligned(16))) float smem[SMEM_FLOATS];
-#endif
     float (*As)[LD] = reinterpret_cast<float (*)[LD]>(smem);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int tiles_m = (g.M + BMN - 1) / BMN, tiles_n = (g.N + BMN - 1) / BMN;
     const int n_tiles = tiles_m * tiles_n;
-    constexpr bool PERSIST = CDX_GEMM_PERSIST && NW == 8 && FAST;
-    const int vb_end = PERSIST ? n_tiles * k_split : (int)blockIdx.x + 1;
-    bool prefetched = false;
+    // One tile per workgroup, yet inside a ONE-TRIP loop, with ra / rb declared ahead of it: what is left of the persistent tile walk of
+    // round 6 (several tiles per workgroup, the next tile's first K tile requested before the epilogue: no gain over one tile per
+    // workgroup).  The wrapper alone changes hipcc's schedule of every instantiation and was worth +1-3 % on the long-K GEMMs
+    // (profiles/r06_gemm_persistent_ab.txt, section (b)) -- it is load-bearing: do not unwrap it without measuring.
+    const int vb_end = (int)blockIdx.x + 1;
     float4 ra[NLD], rb[NLD];
-  for (int vb = blockIdx.x; vb < vb_end; vb += (PERSIST ? (int)gridDim.x : 1 << 30)) {
+  for (int vb = blockIdx.x; vb < vb_end; vb += 1 << 30) {
     const int lin = vb % n_tiles, slice = vb / n_tiles;     // split-K: slice of the K range
     // Tiles are walked n-fastest: concurrently resident workgroups share a few A row blocks across all their N tiles (the whole W
     // fits L2), instead of re-fetching each A block N/128 times -- measured +15-17 % on the config-4/5 shapes over m-fastest.
@@ -384,19 +347,16 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : (WT == 2 ? 3 : 4))) void cd
 
     // Two LDS stages, ONE barrier per K tile: while the MFMAs of tile t run out of stage t & 1, the registers
     // holding tile t + 1 (fetched a whole tile earlier) are written to the other stage and tile t + 2 is requested.
-    if (!(PERSIST && prefetched)) fetch(kt0);            // (persistent walk: requested before the previous tile's epilogue)
+    fetch(kt0);
     stage(0);
     if (nk > 1) fetch(kt0 + BK);
     __syncthreads();
     gm_stamp(1);
-#if CDX_GEMM_KBLOCK
     f32x16 blk[WT];
 #pragma unroll
     for (int i = 0; i < WT; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) blk[i][r] = 0.f;
-#endif
-#if CDX_GEMM_KBLOCK
     if constexpr (NW == 8) {
         // 8-wave shape: two row blocks x one column block per wave = two independent chains; the block accumulators run over TWO K
         // tiles (the second tile continues the chains of the first), then both are flushed into the totals
@@ -424,20 +384,16 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : (WT == 2 ? 3 : 4))) void cd
             }
             __syncthreads();                             // stage (t+1)&1 complete, stage t&1 free for tile t + 2
         };
-        for (int t = 0; t < nk; t += (BK == 32 ? 1 : 2)) {
+        for (int t = 0; t < nk; t += 2) {
             tile8(t, std::true_type{});
-            if (BK != 32 && t + 1 < nk) tile8(t + 1, std::false_type{});
+            if (t + 1 < nk) tile8(t + 1, std::false_type{});
 #pragma unroll
             for (int i = 0; i < 2; ++i) gm_flush(acc[i][0], blk[i]);
         }
     } else
-#else
-    static_assert(NW == 4, "the 8-wave shape exists for the K-blocked accumulation");
-#endif
     for (int t = 0; t < nk; ++t) {
         const float (*Ac)[LD] = As + (t & 1) * (2 * BK);
         const float (*Bc)[LD] = Ac + BK;
-#if CDX_GEMM_KBLOCK
         // K-BLOCKED accumulation (round 5): the products of ONE K tile are summed in block accumulators that start at zero, and the block
         // sums are added to the running totals -- an element's rounding error grows with sqrt(K / BK) + sqrt(BK) roundings instead of
         // the sqrt(K) of one sequential fma chain (profiles/r05_dit_error_budget.txt: K = 320 3.1e-6 -> 0.8e-6 of the output's rms,
@@ -470,7 +426,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : (WT == 2 ? 3 : 4))) void cd
                 }
 #pragma unroll
                 for (int j = 0; j < WT; ++j) blk[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv[j], blk[j], 0, 0, 0);
-                if (h == 0 && kk == (WT == 2 ? GM_STAGE_AT : BK / 2 - 4) && t + 1 < nk) {   // park tile t + 1 in the other stage, request t + 2
+                if (h == 0 && kk == (WT == 2 ? BK - 4 : BK / 2 - 4) && t + 1 < nk) {   // park tile t + 1 in the other stage, request t + 2
                     stage((t + 1) & 1);
                     if (t + 2 < nk) fetch(kt0 + (t + 2) * BK);
                 }
@@ -481,31 +437,6 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : (WT == 2 ? 3 : 4))) void cd
 #pragma unroll
             for (int j = 0; j < WT; ++j) gm_flush(acc[h][j], blk[j]);
         }
-#else
-        // operands of the next k pair are read from LDS before the MFMAs of the current one are issued
-        float av[WT], bv[WT];
-#pragma unroll
-        for (int i = 0; i < WT; ++i) { av[i] = Ac[lk][wm + 32 * i + lr]; bv[i] = Bc[lk][wn + 32 * i + lr]; }
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += 2) {
-            float na[WT], nb[WT];
-#pragma unroll
-            for (int i = 0; i < WT; ++i) {
-                na[i] = 0.f; nb[i] = 0.f;
-                if (kk + 2 < BK) { na[i] = Ac[kk + 2 + lk][wm + 32 * i + lr]; nb[i] = Bc[kk + 2 + lk][wn + 32 * i + lr]; }
-            }
-#pragma unroll
-            for (int i = 0; i < WT; ++i)
-#pragma unroll
-                for (int j = 0; j < WT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[j], acc[i][j], 0, 0, 0);
-            if (kk == BK / 2 - 4 && t + 1 < nk) {        // mid-tile: park tile t + 1 in the other stage, request tile t + 2
-                stage((t + 1) & 1);
-                if (t + 2 < nk) fetch(kt0 + (t + 2) * BK);
-            }
-#pragma unroll
-            for (int i = 0; i < WT; ++i) { av[i] = na[i]; bv[i] = nb[i]; }
-        }
-#endif
         __syncthreads();                                 // stage (t+1)&1 complete, stage t&1 free for tile t + 2
     }
 
@@ -514,28 +445,6 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : (WT == 2 ? 3 : 4))) void cd
     // (the loop's last barrier already separates the final LDS reads from the patches written below)
     // fused epilogue, one specialisation per activation (the branch is uniform; only the taken copy touches the I-cache)
     const int row0 = bm + wm, col0 = bn + wn;
-    if constexpr (PERSIST) {
-        // the NEXT tile of this workgroup: its first K tile is requested now and lands during the epilogue below (plain GEMMs only: a
-        // conv's tap validity belongs to the tile's own set-up)
-        prefetched = false;
-        const int vn = vb + (int)gridDim.x;
-        if (vn < vb_end && !conv) {
-            const int ln = vn % n_tiles, sn = vn / n_tiles;
-            int tn = ln;
-            if (xcd_order) {
-                const int xcd = ln & 7, t = ln >> 3, q8 = n_tiles >> 3, r8 = n_tiles & 7;
-                tn = xcd * q8 + min(xcd, r8) + t;
-            }
-            const int bmn_ = (tn / tiles_n) * BMN, bnn_ = (tn % tiles_n) * BMN;
-            const int ktn = sn * per * BK;
-#pragma unroll
-            for (int i = 0; i < NLD; ++i) {
-                ra[i] = *reinterpret_cast<const float4*>(g.A + (size_t)min(bmn_ + lrow[i], g.M - 1) * g.lda + q4 + ktn);
-                rb[i] = *reinterpret_cast<const float4*>(g.W + (size_t)min(bnn_ + lrow[i], g.N - 1) * g.ldw + q4 + ktn);
-            }
-            prefetched = true;
-        }
-    }
     float* patch = smem + wave * (32 * GM_EP_LD);
     const bool fe = fast_ep != 0;
     if (k_split > 1) {                                   // raw partial tile; the epilogue runs in gm_splitk_reduce_kernel
@@ -544,7 +453,6 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : (WT == 2 ? 3 : 4))) void cd
         gp.bias = nullptr; gp.gate = nullptr; gp.residual = nullptr; gp.table = nullptr;
         gm_epilogue_any<CDX_ACT_NONE, WTM, WTN>(gp, acc, patch, row0, col0, lane, (g.N % 4 == 0));
         gm_stamp(3);
-        if (PERSIST) { __syncthreads(); continue; }
         return;
     }
     switch (g.act) {
@@ -558,7 +466,6 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : (WT == 2 ? 3 : 4))) void cd
         default: gm_epilogue_any<CDX_ACT_NONE, WTM, WTN>(g, acc, patch, row0, col0, lane, fe); break;
     }
     gm_stamp(3);
-    if (PERSIST) __syncthreads();                        // the patches alias the staging area of the next tile
   }
 }
 
@@ -1540,8 +1447,7 @@ __device__ __forceinline__ float gm_act_grad(float x, int act, float param) {
         case CDX_ACT_GELU_ERF: {                         // Phi(x) + x phi(x)
             const float z = fabsf(x) * 0.70710678118654752f;
             const float t = 1.0f / fmaf(0.3275911f, z, 1.0f);
-            const float poly = t * fmaf(t, fmaf(t, fmaf(t, fmaf(t, 1.061405429f, -1.453152027f), 1.421413741f), -0.284496736f), 0.254829592f);
-            const float erf_abs = 1.0f - poly * __expf(-z * z);
+            const float erf_abs = 1.0f - cdx_erf_poly(t) * __expf(-z * z);
             return 0.5f * (1.0f + copysignf(erf_abs, x)) + x * 0.3989422804014327f * __expf(-0.5f * x * x);
         }
         default: return 1.0f;
@@ -1616,9 +1522,8 @@ static int gm_launch(const cdx_gemm_args* g_in, void* hip_stream, bool force_sma
     static const char* env_w8 = getenv("CDX_GEMM_W8");
     const bool aligned16 = (g->lda % 4 == 0) && (g->ldw % 4 == 0) && (((uintptr_t)g->A | (uintptr_t)g->W) % 16 == 0) &&
                            (g->conv_taps == 0 || g->conv_cin % 4 == 0);
-    const bool w8 = CDX_GEMM_KBLOCK && !small && aligned16 && g->K % CDX_GEMM_W8_BK == 0 && g->K % 16 == 0 &&
-                    (env_w8 ? atoi(env_w8) != 0 : CDX_GEMM_W8_DEFAULT);
-    const int bmn = small ? 64 : 128, bk = small ? 32 : (w8 ? CDX_GEMM_W8_BK : 16);
+    const bool w8 = !small && aligned16 && g->K % 16 == 0 && (!env_w8 || atoi(env_w8) != 0);   // (on by default: profiles/r05_gemm_w8_ab.txt)
+    const int bmn = small ? 64 : 128, bk = small ? 32 : 16;
     const int tiles = ((g->M + bmn - 1) / bmn) * ((g->N + bmn - 1) / bmn);
     if (g->conv_taps < 0 || (g->conv_taps > 0 && (g->conv_cin <= 0 || g->conv_lin <= 0 || g->conv_lout <= 0 || g->conv_stride <= 0 ||
                                                    g->K != g->conv_taps * g->conv_cin || g->M % g->conv_lout != 0))) {
@@ -1663,28 +1568,9 @@ static int gm_launch(const cdx_gemm_args* g_in, void* hip_stream, bool force_sma
                         (!g->residual || g->ldr % 4 == 0) && (ep_ptrs % 16 == 0);
     static const char* env_x = getenv("CDX_GEMM_XCD_ORDER");      // tuning hook: 1 = one contiguous tile range per XCD
     const int xcd_order = env_x ? atoi(env_x) : 1;    // rounds 3-5: +-2 % either way; on the round-6 build +1-2 % for DiT / ChiTransformer, neutral elsewhere
-#if CDX_GEMM_PERSIST
-    static const char* env_ps = getenv("CDX_GEMM_PERSIST_SLOTS");    // workgroups of a persistent launch (default: two per CU)
-    const int slots_ps = env_ps && atoi(env_ps) > 0 ? atoi(env_ps) : 512;
-    const dim3 grid(w8 && vec ? (tiles * k_split < slots_ps ? tiles * k_split : slots_ps) : tiles * k_split), block(w8 ? 512 : GM_THREADS);
-#else
     const dim3 grid(tiles * k_split), block(w8 ? 512 : GM_THREADS);
-#endif
-    const size_t lds8 = CDX_GEMM_W8_BK == 32 ? (size_t)4 * 32 * 130 * sizeof(float) : 0;
-    if (w8 && lds8) {
-        static bool raised[2] = {false, false};
-        const int ci = g->conv_taps > 0 ? 1 : 0;
-        if (!raised[ci]) {
-            const void* fn = ci ? reinterpret_cast<const void*>(cdx_gemm_kernel<true, 2, true, 8>) : reinterpret_cast<const void*>(cdx_gemm_kernel<true, 2, false, 8>);
-            raised[ci] = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8) == hipSuccess;
-        }
-    }
 #define GM_LAUNCH(F, W, C) hipLaunchKernelGGL((cdx_gemm_kernel<F, W, C>), grid, block, 0, s, *g, fast_ep, k_split, xcd_order)
-#if CDX_GEMM_KBLOCK
-#define GM_LAUNCH8(C) hipLaunchKernelGGL((cdx_gemm_kernel<true, 2, C, 8>), grid, block, lds8, s, *g, fast_ep, k_split, xcd_order)
-#else
-#define GM_LAUNCH8(C) GM_LAUNCH(true, 2, C)
-#endif
+#define GM_LAUNCH8(C) hipLaunchKernelGGL((cdx_gemm_kernel<true, 2, C, 8>), grid, block, 0, s, *g, fast_ep, k_split, xcd_order)
     const bool cv = g->conv_taps > 0;
     if (small) {
         if (vec) { if (cv) GM_LAUNCH(true, 1, true); else GM_LAUNCH(true, 1, false); }

@@ -22,6 +22,7 @@
 #include <stdio.h>
 
 #include "../../include/cdx.h"
+#include "cdx_act.h"
 
 extern void cdx_set_err(const char* msg);
 
@@ -45,20 +46,6 @@ struct RoArgs {
     cdx_rollout r;
     RoStep st[CDX_ROLLOUT_MAX_STEPS];
 };
-
-// Mish / Mish' of cdx_act_f32 / cdx_act_bwd_f32 (csrc/cdx_gemm.hip: gm_act)
-__device__ __forceinline__ float ro_mish(float x) {
-    const float e = __expf(fminf(x, 20.0f));
-    const float n = e * (e + 2.0f);
-    return x > 20.0f ? x : x * n * __builtin_amdgcn_rcpf(n + 2.0f);
-}
-__device__ __forceinline__ float ro_mish_grad(float x) {     // t + x (1 - t^2) sigmoid(x), t = tanh(softplus x)
-    const float e = __expf(fminf(x, 20.0f));
-    const float n = e * (e + 2.0f);
-    const float t = x > 20.0f ? 1.0f : n / (n + 2.0f);
-    const float sg = e / (1.0f + e);
-    return t + x * (1.0f - t * t) * sg;
-}
 
 // four consecutive k of one weight column n (zero outside the matrix).  TRANS = false: the weight is (N, K) row-major (nn.Linear.weight
 // in a forward product), TRANS = true: (K, N) row-major (the same tensor in the transposed product of the backward pass: 16 lanes x 4 B
@@ -177,7 +164,7 @@ __global__ __launch_bounds__(256) void cdx_rollout_fwd_kernel(const RoArgs a) {
             float* H = r.H + (size_t)l * SBW + (size_t)s * B * W;
             ro_product<false>(src, ld, w, K, W, K, lane, wave, [&](int rr, int n, float v) {
                 const float z = v + bias[n];
-                const float h = ro_mish(z);
+                const float h = cdx_act_mish(z);
                 dst[rr * ld + n] = h;
                 const int row = row0 + rr;
                 if (row < B) {
@@ -313,7 +300,7 @@ __global__ __launch_bounds__(256) void cdx_rollout_bwd_kernel(const RoArgs a) {
                 const int row = row0 + rr;
                 float gz = 0.f;
                 if (row < B) {
-                    gz = v * ro_mish_grad(Z[(size_t)row * W + n]);
+                    gz = v * cdx_act_mish_grad(Z[(size_t)row * W + n]);
                     Z[(size_t)row * W + n] = gz;
                 }
                 dst[rr * ld + n] = gz;

@@ -31,6 +31,7 @@
 #include <string.h>
 
 #include "../../include/cdx.h"
+#include "cdx_act.h"
 #include "cdx_ops2.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -59,6 +60,7 @@ template <int NWV> struct WG {
 
 namespace {
 
+// (not cdx_act_mish: that one selects x for x > 20; this one does without the select, on purpose)
 __device__ __forceinline__ float mish2(float x) {
     // x * tanh(softplus(x)), tanh(log(1+e^x)) = n / (n + 2), n = e^x (e^x + 2); softplus threshold 20 as ATen
     const float e = __expf(fminf(x, 20.0f));
@@ -108,15 +110,16 @@ __device__ __forceinline__ float seg_sum(float v, int w_log2, int lane) {
 __device__ __forceinline__ float act2_f(float x, int id) {
     switch (id) {
         case 2: return mish2(x);                                         // CDX_ACT_MISH
-        case 3: {                                                        // CDX_ACT_GELU_ERF: erf by Abramowitz-Stegun 7.1.26, |err| < 1.5e-7
-            const float z = fabsf(x) * 0.70710678118654752f;
+        case 3: {                                                        // CDX_ACT_GELU_ERF: cdx_act_gelu_erf written out -- through the call (or
+            const float z = fabsf(x) * 0.70710678118654752f;             // cdx_erf_poly alone) hipcc schedules the MLP program kernel differently
             const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
             const float poly = t * fmaf(t, fmaf(t, fmaf(t, fmaf(t, 1.061405429f, -1.453152027f), 1.421413741f), -0.284496736f), 0.254829592f);
             return 0.5f * x * (1.0f + copysignf(1.0f - poly * __expf(-z * z), x));
         }
-        case 4: return x > 0.f ? x : 0.01f * x;                          // CDX_ACT_LEAKY
-        case 5: return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x));     // CDX_ACT_SILU
-        case 6: return fmaxf(x, 0.f);                                    // CDX_ACT_RELU
+        case 4: return cdx_act_leaky(x);                                 // CDX_ACT_LEAKY
+        case 5: return cdx_act_silu(x);                                  // CDX_ACT_SILU
+        case 6: return cdx_act_relu(x);                                  // CDX_ACT_RELU
+        // (GELU_TANH and TANH go through libm's tanhf here, not the exp / rcp forms of cdx_act.h: other roundings)
         case 7: return 0.5f * x * (1.0f + tanhf(0.7978845608028654f * (x + 0.044715f * x * x * x)));   // CDX_ACT_GELU_TANH
         case 9: return tanhf(x);                                         // CDX_ACT_TANH
         default: return x;                                               // 1 = CDX_ACT_NONE
@@ -189,36 +192,15 @@ __device__ __forceinline__ void stamp(unsigned long long* slot, int tid) {
 }
 
 // ---- weight records: loaded through a raw buffer descriptor (uniform byte offset in an SGPR, lane * 16 in one VGPR -- no 64-bit
-// vector address arithmetic per load: +2.4 % at two trajectories per workgroup) with a compile-time cache policy (CDX2_WPOLICY:
-// 0 default, 1 sc0, 2 nt, 16 sc1).  Measured on MI355X: sc0 / sc1 change nothing; nt is 30-40 % SLOWER -- every CU of an XCD streams
+// vector address arithmetic per load: +2.4 % at two trajectories per workgroup) with the default cache policy (last argument of the
+// load: 0 default, 1 sc0, 2 nt, 16 sc1).  Measured on MI355X: sc0 / sc1 change nothing; nt is 30-40 % SLOWER -- every CU of an XCD streams
 // the same records, and non-temporal lines do not stay in the L2 for the other 31.
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-#ifndef CDX2_WPOLICY
-#define CDX2_WPOLICY 0
-#endif
-#ifndef CDX2_PARAMS_ALL
-#define CDX2_PARAMS_ALL 0           // non-pipelined position only: 1 = every wave issues all five parameter loads (see load_params)
-#endif
 #define CDX2_N_CUS 256                            /* MI355X: 8 XCDs x 32 CUs */
 #define CDX2_GETREG_XCC_ID ((3 << 11) | 20)      /* s_getreg_b32 hwreg(HW_REG_XCC_ID, 0, 4): the XCD this wave runs on, 0-7 */
-#ifndef CDX2_XCHG_FAST
-#define CDX2_XCHG_FAST 1            // 0: grouped ops exchange through split_exchange (epilogue -> barrier -> publish -> collect, rounds 4-5)
-#endif
-#ifndef CDX2_XCHG_NOWAIT
-#define CDX2_XCHG_NOWAIT 0          // 1 (diagnostic, WRONG results): grouped ops do not collect at all -- what a fully hidden exchange would cost
-#endif
-#ifndef CDX2_PROF_FETCH
-#define CDX2_PROF_FETCH 0           // diagnostic builds: the PROF kernels' stamps 4-6 time the parts of fetch_next (1) / of the exchange (2) instead of the K loop's
-#endif
-#ifndef CDX2_PIPE_PARAMS
-#define CDX2_PIPE_PARAMS 1          // 0: fetch an op's epilogue parameters and the next descriptor at the op's start (round-2 order)
-#endif
-#ifndef CDX2_MUL24
-#define CDX2_MUL24 1                // 0: plain 32-bit multiplies in the per-op address arithmetic (rounds 2-5)
-#endif
 // Per-lane products of small numbers (LDS offsets, positions x strides: far below 2^23): v_mul_i32_i24 / v_mad_i32_i24 run at full
 // rate, v_mul_lo_u32 / v_mad_u64_u32 at a quarter of it -- on the serial per-op path every instruction is ~7 cycles x 40 ops x 20 steps.
-static __device__ __forceinline__ int mul24i(int a, int b) { return CDX2_MUL24 ? __mul24(a, b) : a * b; }
+static __device__ __forceinline__ int mul24i(int a, int b) { return __mul24(a, b); }
 static __device__ __forceinline__ int wave_of(int tid) { return __builtin_amdgcn_readfirstlane(tid >> 6); }
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wold-style-cast"
@@ -229,7 +211,7 @@ struct WStream {
         : rs(__builtin_amdgcn_make_buffer_rsrc((void*)wblob, 0, 0x7fffffff, 0x00020000)), lane16(lane * 16) {}
     // record `q` of the stream that starts at float offset `woff`
     __device__ __forceinline__ f32x4 load(int woff, int q) const {
-        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, lane16, woff * 4 + q * 1024, CDX2_WPOLICY));
+        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, lane16, woff * 4 + q * 1024, 0));
     }
 };
 #pragma clang diagnostic pop
@@ -278,7 +260,7 @@ __device__ __forceinline__ void conv_kloop(const Geom& g, const float* __restric
             cur[nt] = it.src + __mul24(row, it.sstr) + M::koff(lane) + cc * M::KSTEP;
             tstep[nt] = (valid ? it.sstr : 0) - ccn * M::KSTEP;
         }
-        if (PROF && !CDX2_PROF_FETCH && prof && item == 0) { asm volatile("" ::"s"(nq), "v"(cur[0])); stamp(prof + 4, ptid); }
+        if (PROF && prof && item == 0) { asm volatile("" ::"s"(nq), "v"(cur[0])); stamp(prof + 4, ptid); }
         f32x4 acc[T][NT][NA];
 #pragma unroll
         for (int t = 0; t < T; ++t)
@@ -338,7 +320,7 @@ __device__ __forceinline__ void conv_kloop(const Geom& g, const float* __restric
                 }
             }
         }
-        if (PROF && !CDX2_PROF_FETCH && prof && item == 0) { asm volatile("" ::"v"(wr[0][0]), "v"(bq[0][0][0][0])); stamp(prof + 5, ptid); }
+        if (PROF && prof && item == 0) { asm volatile("" ::"v"(wr[0][0]), "v"(bq[0][0][0][0])); stamp(prof + 5, ptid); }
         // two waves per SIMD: the arbiter favours the older wave (0-3), which then finishes its K loop well before its
         // SIMD-mate and leaves it running alone at the single-wave rate; raising the younger wave's priority evens them out
 
@@ -434,7 +416,7 @@ __device__ __forceinline__ void conv_kloop(const Geom& g, const float* __restric
             }
         }
         if (NWV == 8) __builtin_amdgcn_s_setprio(0);
-        if (PROF && !CDX2_PROF_FETCH && prof && item == 0) { asm volatile("" ::"v"(acc[0][0][0][0]), "v"(acc[0][0][1][0])); stamp(prof + 6, ptid); }
+        if (PROF && prof && item == 0) { asm volatile("" ::"v"(acc[0][0][0][0]), "v"(acc[0][0][1][0])); stamp(prof + 6, ptid); }
         // D fragment: 4 consecutive rows (channels) of one column -> stage[k slice][output position][row tile + rows]
 #pragma unroll
         for (int t = 0; t < T; ++t)
@@ -625,6 +607,7 @@ __device__ __forceinline__ void epilogue(float* __restrict__ tl, const EpiParams
 }
 
 // d Mish(a) / d a with tanh(softplus(a)) = n / (n + 2), n = e^a (e^a + 2):  n/(n+2) + a * 4 e^a (e^a + 1) / (n + 2)^2
+// (not cdx_act_mish_grad: that one is t + a (1 - t^2) sigmoid(a) -- other algebra, other roundings)
 __device__ __forceinline__ float mish2_grad(float a) {
     const float e = __expf(fminf(a, 20.0f));
     const float n = e * (e + 2.0f);
@@ -772,11 +755,10 @@ __device__ __forceinline__ void prefetch_ring(const Item& it, const float* __res
 }
 
 // The five per-channel epilogue parameters of the op whose descriptor view is `vd` (bias, post-norm bias, gamma, beta, FiLM vector).
-// ALL = false: only the waves that run epilogues load, and only what the op's flags ask for (a 64-lane float4 load is 1 KiB through the
-// CU's address path, ~16 cycles each: 8 waves x 5 unconditional loads cost ~450 cycles per op, measured).  That is the right form when
-// the loads sit after the K loop (PIPE).  ALL = true: every wave issues all five (an unused one re-reads the bias) -- for the round-2
-// position at the op's start, where loads on only some paths make hipcc fall back to `s_waitcnt vmcnt(0)` in the K loop.
-template <bool COND, bool SPLIT_T, bool ALL, bool MLP = false, bool GRP = false>
+// Only the waves that run epilogues load, and only what the op's flags ask for (a 64-lane float4 load is 1 KiB through the CU's address
+// path, ~16 cycles each: 8 waves x 5 unconditional loads cost ~450 cycles per op, measured).  (Round 2 had every wave issue all five at
+// the op's start, where loads on only some paths make hipcc fall back to `s_waitcnt vmcnt(0)` in the K loop.)
+template <bool COND, bool SPLIT_T, bool MLP = false, bool GRP = false>
 __device__ __forceinline__ EpiParams load_params(const cdx_unet2_launch& L, int vd, const float* __restrict__ emb_row, int emb_tstride,
                                                  int tid, int wave, bool epi_wave) {
     const int etid = tid & 255, li = etid & 31;
@@ -792,16 +774,6 @@ __device__ __forceinline__ EpiParams load_params(const cdx_unet2_launch& L, int 
     const bool gn = (flags & (CDX2_F2_GN | CDX2_F2_GNBWD)) != 0;
     const float* __restrict__ pem = emb_row + (COND && SPLIT_T ? (wave >> 2) * emb_tstride : 0) + CDX2_DW(vd, CDX2_W2_EMB) + c;
     EpiParams P;
-    if (ALL) {
-        P.bi = *reinterpret_cast<const f32x4*>(pbi);
-        P.pb = *reinterpret_cast<const f32x4*>(CDX2_DW(vd, CDX2_W2_KPOST) ? L.wblob + CDX2_DW(vd, CDX2_W2_PBIAS) + c : pbi);
-        P.ga = *reinterpret_cast<const f32x4*>(gn ? L.wblob + CDX2_DW(vd, CDX2_W2_GAMMA) + c : pbi);
-        P.be = *reinterpret_cast<const f32x4*>(gn ? L.wblob + CDX2_DW(vd, CDX2_W2_BETA) + c : pbi);
-        P.em = *reinterpret_cast<const f32x4*>((flags & CDX2_F2_EMB) ? pem + ((COND && (flags & CDX2_F2_FILM)) ? coutp : 0) : pbi);
-        P.sc = P.bi;
-        if (COND) P.sc = *reinterpret_cast<const f32x4*>((flags & CDX2_F2_FILM) ? pem : pbi);
-        return P;
-    }
     P.bi = P.ga = P.be = P.em = P.pb = P.sc = (f32x4){0.f, 0.f, 0.f, 0.f};
     if (epi_wave) {
         P.bi = *reinterpret_cast<const f32x4*>(pbi);
@@ -832,7 +804,7 @@ struct OpFetch {
 // live VGPRs: 239 -> 256 at T = 2 guided, measured 2.5 % slower).  Measured on MI355X, same box, against the round-2 order
 // (gpurun r3e / r3f): T = 1 with the parameter loads in FRONT of the staging barrier 4.205 vs 4.227 ms (behind it: 4.264);
 // T = 2 with the loads BEHIND the barrier 5.604 vs 5.659 ms (in front: 5.72) -- hence PARAMS_AFTER_BARRIER = (T >= 2).
-template <int T, bool BWD> constexpr bool pipe_params() { return CDX2_PIPE_PARAMS && T < 3 && !BWD; }
+template <int T, bool BWD> constexpr bool pipe_params() { return T < 3 && !BWD; }
 
 // Split programs (one trajectory over k workgroups of one XCD; engine/program2.py:compile_janner2_split): what a member knows about
 // its group.  After an op that is cut over the members (descriptor word W2_XG) every member publishes the channels it computed into
@@ -889,7 +861,7 @@ __device__ __forceinline__ float* exchange_tile(const XState& X, unsigned seq, i
 //  cycles, is the wait for the slowest member of the group plus one L2 round trip, not the copy.)
 template <int THREADS>
 __device__ __forceinline__ void split_exchange(XState& X, int grp_idx, int xg, int gmap, float* __restrict__ tl, int dst, int dstride,
-                                               int l_out, int c_out, int coutp, int tid, unsigned long long* prof = nullptr) {
+                                               int l_out, int c_out, int coutp, int tid) {
     const int g_lo = xg & 255, g_hi = (xg >> 8) & 255;
     const bool grouped = (xg & (CDX2_XG_GOP | CDX2_XG_TRAJ)) != 0, traj = (xg & CDX2_XG_TRAJ) != 0;
     const int gsh = grouped ? (gmap & 255) : 30, grows = grouped ? (gmap >> 8) : 0;
@@ -918,7 +890,6 @@ __device__ __forceinline__ void split_exchange(XState& X, int grp_idx, int xg, i
             o[1] = (f32x4){v[2], tag, v[3], tag};
         }
     }
-    if (CDX2_PROF_FETCH == 2) stamp(prof ? prof + 5 : nullptr, tid);
     // collect: everybody else's part, straight from L2 (nontemporal loads bypass this CU's L1), as soon as their tags say so.
     // (Measured and dropped, gpurun r4k / r4l: requesting a thread's two items together -- even the same loop merely WRITTEN for two
     //  items with one of them disabled -- is 2 % slower at B = 256 than this plain loop; the poll interval, s_sleep 0 / 1 / 4 / 16, changes
@@ -958,7 +929,7 @@ __device__ __forceinline__ void split_exchange(XState& X, int grp_idx, int xg, i
     }
 }
 
-// Fast exchange of a grouped op (CDX2_XCHG_FAST): the epilogue waves publish their items from registers (epilogue<..., PUBLISH>) while
+// Fast exchange of a grouped op: the epilogue waves publish their items from registers (epilogue<..., PUBLISH>) while
 // the OTHER four waves -- which have nothing to do during an epilogue but halo rows -- collect the other members' parts: thread u of
 // the 256 takes tile item (position u >> nc4sh, float4 u & (nc4 - 1)) of each of the k - 1 other members' channel blocks, requests all of
 // them at once (up to six 16-byte loads in flight) and polls until every tag matches.  Round-5 form (split_exchange): epilogue ->
@@ -1043,13 +1014,10 @@ __device__ __forceinline__ void run_op(const cdx_unet2_launch& L, const cint* op
     // issues those AFTER its staging barrier instead (see pipe_params)
     auto fetch_next = [&](bool params) {
         it = inline_item(vdn);
-        if (PROF && CDX2_PROF_FETCH == 1) stamp(prof ? prof + 4 : nullptr, tid);
         if (wave_of(tid) < CDX2_DW(vdn, CDX2_W2_NITEMS)) prefetch_ring(it, L.wblob, tid & 63, ring);
-        if (PROF && CDX2_PROF_FETCH == 1) stamp(prof ? prof + 5 : nullptr, tid);
         if (PIPE) {
             if (params)
-                F.P = load_params<COND, SPLIT_T, false, MLP, MEMBER>(L, vdn, emb_next, emb_next_tstride, tid, wave_of(tid), NWV == 4 || SPLIT_T || wave_of(tid) < 4);
-            if (PROF && CDX2_PROF_FETCH == 1) stamp(prof ? prof + 6 : nullptr, tid);
+                F.P = load_params<COND, SPLIT_T, MLP, MEMBER>(L, vdn, emb_next, emb_next_tstride, tid, wave_of(tid), NWV == 4 || SPLIT_T || wave_of(tid) < 4);
             F.vdn2 = load_desc<NWV>(L.ops, op_next2 + (MEMBER ? X->m * L.n_ops : 0), tid & 63, wave_of(tid));
         }
     };
@@ -1121,7 +1089,7 @@ __device__ __forceinline__ void run_op(const cdx_unet2_launch& L, const cint* op
     const int pos0 = li >> shift, pstep = 32 >> shift;
     const int nv = (coutp >> 5) * l_out;
     // this op's epilogue parameters: fetched during the PREVIOUS op (PIPE), or here (consumed after the barrier either way)
-    EpiParams P = PIPE ? F.P : load_params<COND, SPLIT_T, CDX2_PARAMS_ALL != 0, MLP, MEMBER>(L, vd, emb_row, emb_tstride, tid, wave, epi_wave);
+    EpiParams P = PIPE ? F.P : load_params<COND, SPLIT_T, MLP, MEMBER>(L, vd, emb_row, emb_tstride, tid, wave, epi_wave);
 
     // K loop -> staged partial tiles
     const int n_items = CDX2_DW(vd, CDX2_W2_NITEMS);
@@ -1148,7 +1116,7 @@ __device__ __forceinline__ void run_op(const cdx_unet2_launch& L, const cint* op
     if (PROF) stamp(prof ? prof + 1 : nullptr, tid);
     __syncthreads();
     if (PROF) stamp(prof ? prof + 2 : nullptr, tid);
-    const EpiParams Pnext = PARAMS_AFTER_BARRIER ? load_params<COND, SPLIT_T, false, MLP, MEMBER>(L, vdn, emb_next, emb_next_tstride, tid, wave, epi_wave)
+    const EpiParams Pnext = PARAMS_AFTER_BARRIER ? load_params<COND, SPLIT_T, MLP, MEMBER>(L, vdn, emb_next, emb_next_tstride, tid, wave, epi_wave)
                                                  : (PIPE ? F.P : P);
 
     const EpiDesc e = decode_epi<BWD>(vd);
@@ -1169,7 +1137,7 @@ __device__ __forceinline__ void run_op(const cdx_unet2_launch& L, const cint* op
         // first one), K slices `k x l_out` positions apart.  Every half-wave works.
         const int gx_lo = xgw & 255, gpm = ((xgw >> 8) & 255) - gx_lo, grows = gmap >> 8;
         // fast exchange: the epilogue threads publish, the other waves collect meanwhile (collect_fast); X->seq moves on below
-        const bool xfast = CDX2_XCHG_FAST && (xgw & CDX2_XG_XCHG) != 0;
+        const bool xfast = (xgw & CDX2_XG_XCHG) != 0;
         const unsigned xseq = X->seq + 1;
         float* xtile = xfast ? exchange_tile(*X, xseq, __float_as_int(lds[T * tf])) : nullptr;
         if (epi_wave) {
@@ -1240,21 +1208,18 @@ __device__ __forceinline__ void run_op(const cdx_unet2_launch& L, const cint* op
                 *reinterpret_cast<f32x4*>(lds + dbase + (tt * hrows + hrow) * e.dstride + j) = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
     if (PIPE) F.P = Pnext;
-    if (SPLIT && CDX2_XCHG_FAST && (xgw & CDX2_XG_GOP) && (xgw & CDX2_XG_XCHG)) {
+    if (SPLIT && (xgw & CDX2_XG_GOP) && (xgw & CDX2_XG_XCHG)) {
         // grouped op, fast exchange: the halo waves collect while the epilogue waves still compute and publish
         const unsigned xseq = X->seq + 1;
-        if (halo_wave && !CDX2_XCHG_NOWAIT) {
+        if (halo_wave) {
             const int gi = __float_as_int(lds[T * tf]);
             collect_fast(*X, gi, xseq, exchange_tile(*X, xseq, gi), xgw, gmap, lds, e.dst, e.dstride, l_out, e.coutp, tid & 255);
         }
         X->seq = xseq;
     } else
     if (SPLIT && (xgw & CDX2_XG_XCHG)) {
-        if (PROF && CDX2_PROF_FETCH == 2) stamp(prof ? prof + 4 : nullptr, tid);
         __syncthreads();                                             // the epilogue's stores to the destination slot are in LDS
-        split_exchange<WG<NWV>::THREADS>(*X, __float_as_int(lds[T * tf]), xgw, gmap, lds, e.dst, e.dstride, l_out, e.c_out, e.coutp, tid,
-                                         (PROF && CDX2_PROF_FETCH == 2) ? prof : nullptr);
-        if (PROF && CDX2_PROF_FETCH == 2) stamp(prof ? prof + 6 : nullptr, tid);
+        split_exchange<WG<NWV>::THREADS>(*X, __float_as_int(lds[T * tf]), xgw, gmap, lds, e.dst, e.dstride, l_out, e.c_out, e.coutp, tid);
     }
     __syncthreads();
     if (PROF) stamp(prof ? prof + 3 : nullptr, tid);
@@ -1408,7 +1373,7 @@ __global__ __launch_bounds__(NWV * 64, (NWV == 8 || T == 1) ? 2 : 1) void cdx_un
     if (PIPE) {
         int ts0;
         const float* row0 = emb_of(0, 0, ts0);
-        F.P = load_params<COND, SPLIT_T0, false, MLP>(L, vd, row0, ts0, tid, wave, NWV == 4 || SPLIT_T0 || wave < 4);
+        F.P = load_params<COND, SPLIT_T0, MLP>(L, vd, row0, ts0, tid, wave, NWV == 4 || SPLIT_T0 || wave < 4);
         vdn_keep = load_desc<NWV>(L.ops, moff + (L.n_ops > 1 ? 1 : 0), lane, wave);
     }
     for (int step = 0; step < n_iter; ++step) {

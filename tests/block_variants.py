@@ -33,7 +33,6 @@ GUARDED = {
 }
 
 EXCLUDED = {
-    # (a CDX_GEMM_PERSIST=1 build changes the grid of the 8-wave kernel, not the set of instantiations)
     "cdx_gemm_kernel<true,2,false,4>": "CDX_GEMM_W8=0 (A/B hook: the 4-wave shape of the unguarded 128 x 128 tile)",
     "cdx_gemm_kernel<true,2,true,4>": "CDX_GEMM_W8=0 (A/B hook: the 4-wave shape of the unguarded 128 x 128 tile)",
     "cdx_groupnorm_vec_kernel<true>": "cdx_groupnorm_slices_f32, library-internal: the split-K conv + GroupNorm pair of the sampling "

@@ -15,7 +15,7 @@
 // call = 53-55 % of peak, phase 2 at 57 % of its MFMA floor -- and the ISA of THAT build shows why: the W2 staging registers were a guarded
 // float4[3] that the compiler kept in scratch, every global load followed by s_waitcnt vmcnt(0) and a scratch store.  This file carries the
 // fix (named registers, unconditional clamped loads); it compiles to 0 scratch bytes and has NOT been timed yet.  Two compile-time knobs prepare
-// the first measurements of the next round (tools/gpu_mlp_fused_probe.sh builds and runs all four): PROBE_BK2 (W2 slab of 8 or 16 k) and
+// the first measurements of the next round (tools/build_probes.sh builds all four): PROBE_BK2 (W2 slab of 8 or 16 k) and
 // PROBE_UPFRONT (LDS operands of a slab requested before its first MFMA).  Every build checks itself against the float64 reference.
 //
 //   hipcc --offload-arch=gfx950 -O3 -o tools/_bin/mlp_fused_probe tools/mlp_fused_probe.hip && tools/_bin/mlp_fused_probe
