@@ -653,7 +653,11 @@ __device__ __forceinline__ void epilogue_bwd(float* __restrict__ tl, const EpiPa
         }
         if (ks < e.ksplit) acc += *reinterpret_cast<const f32x4*>(sp);
         if (e.flags & CDX2_F2_RES) acc += *reinterpret_cast<const f32x4*>(tl + e.res + mul24i(pos + CDX2_HALO2, e.rstride) + c);
-        if ((e.flags & CDX2_F2_DUAL) && ok[k]) *reinterpret_cast<f32x4*>(tl + e.dst2 + mul24i(pos + CDX2_HALO2, e.d2stride) + c) = acc;
+        // (lane groups past C_out store nothing here either: a slot of fewer than 8 x 4 channels has a row stride below their `c`, and
+        //  their float4 would land on the NEXT position's real channels -- a race with the lane group that owns them)
+        //  (a GroupNorm layer's C_out is a multiple of 4 -- the lane groups' float4 items --, so a real lane group stores whole vectors)
+        if ((e.flags & CDX2_F2_DUAL) && ok[k] && c < e.c_out)
+            *reinterpret_cast<f32x4*>(tl + e.dst2 + mul24i(pos + CDX2_HALO2, e.d2stride) + c) = acc;
         // (lane groups past C_out -- nets with fewer than 8 x 4 channels -- have nothing saved: zeros, never stored)
         xh[k] = xh_pre[k];
         const f32x4 a = xh[k] * P.ga + P.be;

@@ -954,17 +954,24 @@ def guided_sample2(solver, net, clf_net, plan, xt, prior, feed, fix_mask, x_min,
     return out
 
 
-def classifier_gradient2(net, clf_net, x, noise_t) -> Optional[torch.Tensor]:
-    """d classifier(x, t).sum() / d x through the guided program in forward mode (ONE timestep for the batch) -- test / probe entry."""
+def classifier_gradient2(net, clf_net, x, noise_t, form: Optional[str] = None) -> Optional[torch.Tensor]:
+    """d classifier(x, t).sum() / d x through the guided program in forward mode (ONE timestep for the batch) -- test / probe entry.
+    `form`: None -- the one-trajectory program (all in LDS, or whichever workspace fallback `_compile_guided2` lands on); "two" / "three"
+    -- the two- / three-trajectory programs guided_sample2 takes above B = 256 / 512, at that many trajectories per workgroup.  None when
+    the requested program does not exist."""
+    if form not in (None, "two", "three"):
+        raise ValueError(f"classifier_gradient2: unknown program form {form!r}")
     b, h, d = x.shape
     if guided_supported(net, clf_net, h) is not None:
         return None
-    comp = compiled_guided2(net, clf_net, h)
+    comp = compiled_guided2(net, clf_net, h, two=form == "two", three=form == "three")
+    if comp.prog is None:
+        return None
     with torch.no_grad():
         emb = film_table(comp, net, noise_t.reshape(-1)[:1], modules=[net, clf_net])
         xin = R._f32c(x, x.device)
         out = torch.empty_like(xin)
-        launch(comp, batch=b, x_in=xin, x_out=out, emb=emb, t_per_wg=1, with_backward=True)
+        launch(comp, batch=b, x_in=xin, x_out=out, emb=emb, t_per_wg={None: 1, "two": 2, "three": 3}[form], with_backward=True)
     return out
 
 
