@@ -17,6 +17,8 @@ Architecture (different from the reference on purpose):
      user backbones.
    * **differentiable rollout** (engine/rollout.py -> ``cdx_rollout_fwd_f32`` / ``cdx_rollout_bwd_f32``): ``requires_grad=True`` over
      DQLMlp / DVInvMlp (Diffusion-QL's policy update) -- the loop in one forward and one backward launch.
+   * **energy-guided launch** (engine/energy.py -> ``cdx_energy_guided_run``): QGPO's ``w_cg != 0`` sampling over SfBCUNet with a
+     QGPOClassifier -- denoiser, energy gradient and solver step of every denoising step, and the final log_p, in one launch.
 3. Noise is drawn in exactly the reference's order (initial draw, then one draw per stochastic step) so a CPU run
    with the same torch seed reproduces the reference; ``noise=[z0, z1, ...]`` (kwarg) replays recorded draws,
    which is how device runs are compared with the CPU oracle and how multi-GPU shards stay seed-consistent.
@@ -276,6 +278,9 @@ class BaseDiffusionSDE(DiffusionModel):
             if fused is None and requires_grad:       # DQL's policy update: the differentiable loop in two launches (engine/rollout.py)
                 from ..engine import rollout
                 fused = rollout.try_rollout(self, model, plan, xt, prior, cond_vec, w_cfg, w_cg, feed)
+            if fused is None and not requires_grad and w_cg != 0.0 and self.classifier is not None:
+                from ..engine import energy          # QGPO's energy guidance: the loop and the final log_p in one launch (engine/energy.py)
+                fused = energy.try_energy_guided(self, model, plan, xt, prior, cond_vec, w_cfg, condition_cg, w_cg, feed)
         if fused is not None:
             xt = fused
         else:

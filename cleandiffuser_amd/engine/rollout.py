@@ -159,6 +159,35 @@ def _bounds(q, st, x):
     return q.x_min, q.x_max
 
 
+def reference_step(q, st, ni: int, x, p):
+    """x_{s+1} from x_s and the raw prediction `p`: clip, eps <-> x0, the affine update of the record, `+ k z` (draw `ni` of q.noise),
+    fix-mask blend -- the solver step of the row-tile kernels (csrc/cdx_rollout.hip, csrc/cdx_energy.hip)."""
+    lo, hi = _bounds(q, st, x)
+    if lo is not None:
+        p = torch.maximum(p, lo)
+    if hi is not None:
+        p = torch.minimum(p, hi)
+    k0, k1, k2, k3, _ = st.k
+    if q.predict_noise:
+        eps, xth = p, (x - st.sigma * p) / st.alpha
+    else:
+        eps, xth = (x - st.alpha * p) / st.sigma, p
+    if st.kind == KIND_DDPM:
+        new = k0 * (x - k1 * eps) + k2 * eps
+        if ni >= 0:
+            new = new + k3 * q.noise[ni]
+    elif st.kind == KIND_DDIM:
+        new = k0 * ((x - k1 * eps) / k2) + k3 * eps
+    else:
+        assert st.kind == KIND_LINEAR and st.vsel <= 1
+        new = k0 * x - k1 * (xth if st.vsel == V_XTHETA else eps)
+        if ni >= 0:
+            new = new + k2 * q.noise[ni]
+    if q.fix_mask is not None:
+        new = new * (1. - q.fix_mask) + q.prior * q.fix_mask
+    return new
+
+
 def reference_forward(q) -> None:
     """What ``cdx_rollout_fwd_f32`` computes, step by step, into the same buffers."""
     w1, b1, w2, b2, w3, b3, wh, bh = q.weights
@@ -175,30 +204,7 @@ def reference_forward(q) -> None:
             q.Z[l, s], q.H[l, s] = z, h
         p = h @ wh.t() + bh
         q.P_raw[s] = p
-        lo, hi = _bounds(q, st, x)
-        if lo is not None:
-            p = torch.maximum(p, lo)
-        if hi is not None:
-            p = torch.minimum(p, hi)
-        k0, k1, k2, k3, _ = st.k
-        if q.predict_noise:
-            eps, xth = p, (x - st.sigma * p) / st.alpha
-        else:
-            eps, xth = (x - st.alpha * p) / st.sigma, p
-        if st.kind == KIND_DDPM:
-            new = k0 * (x - k1 * eps) + k2 * eps
-            if ni >= 0:
-                new = new + k3 * q.noise[ni]
-        elif st.kind == KIND_DDIM:
-            new = k0 * ((x - k1 * eps) / k2) + k3 * eps
-        else:
-            assert st.kind == KIND_LINEAR and st.vsel <= 1
-            new = k0 * x - k1 * (xth if st.vsel == V_XTHETA else eps)
-            if ni >= 0:
-                new = new + k2 * q.noise[ni]
-        if q.fix_mask is not None:
-            new = new * (1. - q.fix_mask) + q.prior * q.fix_mask
-        x = new
+        x = reference_step(q, st, ni, x, p)
         q.X[s + 1] = x
 
 

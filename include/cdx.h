@@ -775,6 +775,75 @@ int cdx_rollout_fwd_f32(const cdx_rollout* r, void* hip_stream);
 int cdx_rollout_bwd_f32(const cdx_rollout* r, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * QGPO's energy-guided sampling loop in ONE launch (csrc/cdx_energy.hip).  A purely additive entry: no existing struct or call changes,
+ * so CDX_ABI_VERSION stays 18.  Reference: pipelines/qgpo_d4rl_mujoco.py:244-249 -- ``actor.sample(..., w_cfg=1, condition_cg=obs,
+ * w_cg=w)`` over SfBCUNet (nn_diffusion/sfbc_unet.py:53-82) with QGPOClassifier(QGPONNClassifier) (nn_classifier/mlp.py:25-55), once per
+ * environment step.  One workgroup of 4 wave64 owns 16 rows for the whole loop; per step record s
+ *   denoiser    c = den_c[s] + cond[row];  block(h) = SiLU(W2 (SiLU(W1 h + b1) + Wc c + bc) + b2) + skip(h) for every block of the table --
+ *               the first `n_down` outputs go on a skip stack in LDS, a block with in2 > 0 reads [h | popped skip] as two K ranges of one
+ *               product --, then the out layer: the raw prediction (16 x A);
+ *   energy      f = mlp([obs_proj(obs) | act_proj(x_s) | clf_temb[s]]) with SiLU hidden layers, logp = 10 tanh(f / 10), and
+ *               g = d logp.sum() / d x_s by the explicit backward: x SiLU'(pre), the transposed weights, then through act_proj;
+ *   step        pred += cg_scale[s] * g, then clip, eps <-> x0, the affine update (kinds 0 / 1 / 2, vsel 0 / 1), `+ k z` and the fix-mask
+ *               blend: the arithmetic and order of cdx_rollout_fwd_f32's solver step.
+ * After the last step one more energy forward on the UNCLIPPED x_S with clf_temb[S] gives logp_out (reference diffusionsde.py:943-947);
+ * the final clip of x_out is the caller's.  Everything per step that does not depend on the row is a table the caller computes.
+ * Caller-owned memory, one kernel enqueued on `hip_stream`, no synchronisation, no allocation, capturable; no atomics: bit-reproducible.
+ * Limits (CDX_EINVAL with a message, before anything is launched): every hidden width (block outputs, classifier layers) a multiple of
+ * 16 and <= 512; a concat input in + in2 <= 1024; A <= 64; E, Ec <= 128; O <= 512; 1 <= S <= CDX_ENERGY_MAX_STEPS; kinds 0-2, vsel <= 1,
+ * no flags; a step with noise_idx >= 0 needs `noise`; no null weights or outputs; the LDS plan (cdx_energy_guided_lds_bytes) at most
+ * 160 KiB.  B == 0 is CDX_OK.
+ * ---------------------------------------------------------------------------------------------- */
+#define CDX_ENERGY_MAX_STEPS 64
+#define CDX_ENERGY_MAX_BLOCKS 8
+#define CDX_ENERGY_MAX_HIDDEN 4
+typedef struct cdx_energy_block {
+    int32_t in, in2, out;      /* width of the running activation, of the concat partner popped from the skip stack (or 0), of the output */
+    int32_t reserved;          /* 0 */
+    const float *w1, *b1;      /* (out, in + in2), (out) */
+    const float *w2, *b2;      /* (out, out), (out) */
+    const float *wc, *bc;      /* (out, E), (out) */
+    const float *ws, *bs;      /* (out, in + in2), (out); both NULL = identity skip (in + in2 == out) */
+} cdx_energy_block;
+typedef struct cdx_energy_guided {
+    int32_t B, A, E, O, S, Ec;
+    int32_t n_blocks, n_down;  /* blocks [0, n_down) are the down path; 1 <= n_blocks <= CDX_ENERGY_MAX_BLOCKS */
+    int32_t n_hidden;          /* hidden layers of the classifier's mlp, 1 .. CDX_ENERGY_MAX_HIDDEN */
+    int32_t predict_noise;     /* the denoiser predicts eps (1) or x0 (0) */
+    int32_t clip;              /* 0: x_min / x_max are ignored inside the loop */
+    int32_t hidden[CDX_ENERGY_MAX_HIDDEN];              /* widths of the classifier's hidden layers */
+    const cdx_energy_block* blocks;                     /* HOST [n_blocks] of device pointers */
+    const float *out_w, *out_b;                         /* (A, out of the last block), (A) */
+    const float* den_c;                                 /* (S, E): t_layer(map_noise(t_s)) */
+    const float* cond;                                  /* (B, E) or NULL: zeros (w_cfg = 0) */
+    const float* obs;                                   /* (B, O) */
+    const float *obs_w, *obs_b;                         /* (Ec, O), (Ec) */
+    const float *act_w, *act_b;                         /* (Ec, A), (Ec) */
+    const float* act_wt;                                /* (A, Ec): act_w transposed */
+    const float* clf_w[CDX_ENERGY_MAX_HIDDEN];          /* layer l: (hidden[l], l ? hidden[l-1] : 3 Ec) */
+    const float* clf_b[CDX_ENERGY_MAX_HIDDEN];          /* (hidden[l]) */
+    const float* clf_wt[CDX_ENERGY_MAX_HIDDEN];         /* the backward's operand: l > 0: clf_w[l] transposed (hidden[l-1], hidden[l]); l = 0:
+                                                         * the act_proj columns [Ec, 2 Ec) of clf_w[0] transposed (Ec, hidden[0]) */
+    const float *clf_wo, *clf_bo;                       /* (1, hidden[n_hidden-1]), (1) */
+    const float* clf_temb;                              /* (S + 1, Ec): the classifier's map_noise(t_s); row S is t = 0 */
+    const cdx_step* steps;                              /* HOST [S] */
+    const float* cg_scale;                              /* HOST [S]: the guidance shift of the raw prediction, frozen by the caller */
+    const float* x_in;                                  /* (B, A) */
+    const float* prior;                                 /* (B, A) or NULL */
+    const float* fix_mask;                              /* (A) or NULL */
+    const float* x_min;                                 /* (A) or NULL */
+    const float* x_max;                                 /* (A) or NULL */
+    const float* noise;                                 /* [n_noise][B][A] or NULL */
+    float* x_out;                                       /* (B, A): x_S, unclipped */
+    float* logp_out;                                    /* (B, 1) or NULL */
+    float *trace_pred, *trace_grad;                     /* (S, B, A) or NULL: the unshifted prediction / the gradient g of every step */
+    float* trace_logp;                                  /* (S, B) or NULL: logp of every step */
+} cdx_energy_guided;
+/* bytes of LDS one workgroup of this request needs, or a negative CDX_E* code when the sizes are out of range */
+long long cdx_energy_guided_lds_bytes(const cdx_energy_guided* g);
+int cdx_energy_guided_run(const cdx_energy_guided* g, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimiser side of DiffusionModel.update(): multi-tensor AdamW + EMA + gradient-norm clipping.
  * Replaces, per update() call, torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW.step() + optimizer.zero_grad() +
  * DiffusionModel.ema_update() (reference diffusion/diffusionsde.py:114-141, diffusion/basic.py:66,83-86): one device table of
