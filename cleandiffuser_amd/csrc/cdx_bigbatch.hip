@@ -122,7 +122,8 @@ __global__ void solver_step_kernel(const StepArgs a) {
                 a.x[i] = xn;
                 continue;
             }
-            const float s = (x - d) / k2;
+            float s = (x - d) / k2;
+            if (st.flags & CDX_STEP_MASK_PRED) s *= 1.0f - (a.fix_mask ? a.fix_mask[e] : 0.f);   // legacy EDM masks its slope (edm.py dot_x)
             if (st.kind == 5) {
                 xn = x - s * k3;
                 if (st.push) { a.prev[i] = s; a.xold[i] = x; }

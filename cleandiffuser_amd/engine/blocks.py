@@ -139,6 +139,9 @@ def _lib():
         lib.cdx_relayout_f32.restype = ctypes.c_int
         lib.cdx_gather_windows_f32.argtypes = [ctypes.POINTER(CdxGatherArgs), ctypes.c_void_p]
         lib.cdx_gather_windows_f32.restype = ctypes.c_int
+        lib.cdx_linattn_f32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                        ctypes.c_float, ctypes.c_void_p]
+        lib.cdx_linattn_f32.restype = ctypes.c_int
         for f in (lib.cdx_gemm_f32, lib.cdx_layernorm_f32, lib.cdx_attention_f32, lib.cdx_act_f32):
             f.restype = ctypes.c_int
         _declared = True
@@ -500,6 +503,20 @@ def cross_attention(q: torch.Tensor, kv_shared: torch.Tensor, kv_rows: Optional[
                      B=batch, T=tokens, n_obs=n_obs, n_heads=n_heads, head_dim=dh, shared_row=shared_row,
                      shared_per_sample=int(shared_per_sample), scale=float(dh) ** -0.5)
     _check(_lib().cdx_cross_attention_f32(ctypes.byref(a), _stream_ptr(q.device)), "cdx_cross_attention_f32")
+    return out
+
+
+def linear_attention(qkv: torch.Tensor, batch: int, length: int, heads: int, dim_head: int, scale: Optional[float] = None,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The core of LinearAttention (nn_diffusion/jannerunet.py) per (sample, head): q * scale, softmax of k over the positions,
+    ctx = k v^T, out = ctx^T q.  qkv: (batch * length, 3 * heads * dim_head) rows [q | k | v] -> (batch * length, heads * dim_head)."""
+    inner = heads * dim_head
+    assert qkv.is_contiguous() and qkv.dtype == torch.float32 and qkv.shape == (batch * length, 3 * inner)
+    if out is None:
+        out = torch.empty((batch * length, inner), device=qkv.device, dtype=torch.float32)
+    assert out.is_contiguous() and out.dtype == torch.float32 and out.shape == (batch * length, inner)
+    _check(_lib().cdx_linattn_f32(qkv.data_ptr(), out.data_ptr(), batch, length, heads, dim_head,
+                                  float(dim_head) ** -0.5 if scale is None else float(scale), _stream_ptr(qkv.device)), "cdx_linattn_f32")
     return out
 
 

@@ -39,7 +39,7 @@ class Step:
     k: Tuple[float, float, float, float, float]
     noise: bool = False        # consumes one fresh N(0, I) draw
     push: int = 0              # 1: stores xth (2: eps) for the next multistep update; EDM: stores slope and state
-    flags: int = 0             # F_MASK_PRED: legacy DPMSolver applies the fix-mask to the prediction
+    flags: int = 0             # F_MASK_PRED: legacy DPMSolver applies the fix-mask to the prediction, legacy EDM to its slope
 
 
 @dataclass
@@ -251,7 +251,8 @@ def build_legacy_edm_plan(sigma_data: float, sigma_s: torch.Tensor, solver: str,
     def rec(kind, i, dt, push):
         s = sig[i]
         return Step(kind, V_EPS, i, _f(0.25 * s.log()), _f(1 / (sd2 + s ** 2).sqrt()), _f(s),
-                    (_f(sd2 / (sd2 + s ** 2)), _f(s * sigma_data / (sd2 + s ** 2).sqrt()), _f(s), dt, 0.0), push=push)
+                    (_f(sd2 / (sd2 + s ** 2)), _f(s * sigma_data / (sd2 + s ** 2).sqrt()), _f(s), dt, 0.0), push=push,
+                    flags=F_MASK_PRED)             # dot_x masks the slope: s (1 - fix_mask)
 
     plan = SamplePlan(solver="legacy_edm_" + solver, t_is_integer=False)
     for i in range(n):

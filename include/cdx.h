@@ -37,7 +37,9 @@ extern "C" {
  *   kind 5/6 (EDM Euler / Heun corrector; reference diffusion/newedm.py:387-401, legacy edm.py:118-160,252-268):
  *            `alpha` carries c_in (the network sees c_in*x), k = (c_skip, c_out, sigma, dt):
  *            D = clip(k0*x + k1*F); s = (x - D)/k2;  kind 5: x' = x - k3*s (push: remember s and x);
- *            kind 6: x' = x_old - k3*(s_old + s)/2.
+ *            kind 6: x' = x_old - k3*(s_old + s)/2.  With CDX_STEP_MASK_PRED (legacy EDM class, edm.py:118-160: the slope is
+ *            masked) s <- s*(1-mask) first -- cdx_bigbatch.hip; the in-LDS step of cdx_unet2.hip leaves s as it is, which gives the
+ *            same x' wherever the mask is 0 or 1.
  *   kind 7 (consistency model, reference diffusion/consistency_model.py:412-427): x' = mask(D) [+ k3*z]  (re-noising for
  *            the next level; the fix-mask is applied BEFORE the noise).   A plan is all-EDM-family (5/6/7) or not at all.
  * followed by the fix-mask blend (diffusionsde.py:592). */

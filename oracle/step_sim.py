@@ -33,6 +33,8 @@ def run_plan(plan, net, x, *, predict_noise, prior=None, fix_mask=None, noise=()
                 x = xn + k[3] * next(draws) if st.noise else xn
                 continue
             s = (x - d) / k[2]
+            if st.flags & 1:                     # legacy EDM masks its slope
+                s = s * (1.0 - m)
             if st.kind == 5:
                 xn = x - s * k[3]
                 if st.push:

@@ -129,6 +129,63 @@ def test_attention_with_additive_mask(tokens, heads, dh):
     torch.testing.assert_close(out.cpu().double(), ref, rtol=2e-5, atol=2e-5)
 
 
+def _linear_attention_ref(qkv, B, L, heads, dh, scale):
+    """The core of LinearAttention.forward (nn_diffusion/jannerunet.py) in float64: q * scale, softmax of k over the positions,
+    ctx = k v^T, out = ctx^T q.  Rows are positions, columns [q | k | v] x (head, channel)."""
+    q, k, v = (_ref(qkv).reshape(B, L, 3, heads, dh)[:, :, i].permute(0, 2, 3, 1) for i in range(3))        # (B, heads, dh, L)
+    ctx = torch.einsum("b h d n, b h e n -> b h d e", k.softmax(dim=-1), v)
+    out = torch.einsum("b h d e, b h d n -> b h e n", ctx, q * scale)
+    return out.permute(0, 3, 1, 2).reshape(B * L, heads * dh)
+
+
+# one position / one channel; odd sizes; the shipped shape; 64 KiB of LDS (past the 48 KiB a kernel gets without the attribute); 124 KiB;
+# L > 256: each softmax thread walks a long column and the staging loops take several trips
+@pytest.mark.parametrize("B,L,heads,dh", [(3, 1, 1, 1), (2, 7, 3, 6), (2, 32, 4, 32), (1, 64, 2, 64), (1, 144, 1, 64), (5, 300, 2, 8)])
+def test_linear_attention_matches_float64(B, L, heads, dh):
+    from cleandiffuser_amd.engine import blocks
+    g = torch.Generator().manual_seed(L * 7 + dh)
+    torch.full((1 << 22,), float("nan"), device=DEV)     # whatever stale memory the kernel might touch is poisoned first
+    qkv = torch.randn(B * L, 3 * heads * dh, generator=g) * 2
+    out = blocks.linear_attention(qkv.to(DEV), B, L, heads, dh)
+    assert out.shape == (B * L, heads * dh)
+    torch.testing.assert_close(out.cpu().double(), _linear_attention_ref(qkv, B, L, heads, dh, dh ** -0.5), rtol=2e-5, atol=2e-5)
+    scaled = blocks.linear_attention(qkv.to(DEV), B, L, heads, dh, scale=0.37, out=torch.full_like(out, float("nan")))
+    torch.testing.assert_close(scaled.cpu().double(), _linear_attention_ref(qkv, B, L, heads, dh, 0.37), rtol=2e-5, atol=2e-5)
+
+
+def test_linear_attention_softmax_is_shifted():
+    """k entries of +-80: exp(80) overflows fp32, so a softmax that does not subtract the column maximum gives inf / inf."""
+    from cleandiffuser_amd.engine import blocks
+    g = torch.Generator().manual_seed(80)
+    B, L, heads, dh = 2, 33, 2, 16
+    inner = heads * dh
+    torch.full((1 << 22,), float("nan"), device=DEV)
+    qkv = torch.randn(B * L, 3 * inner, generator=g)
+    qkv[:, inner:2 * inner] = 80.0 * torch.sign(torch.randn(B * L, inner, generator=g))
+    out = blocks.linear_attention(qkv.to(DEV), B, L, heads, dh)
+    assert torch.isfinite(out).all()
+    torch.testing.assert_close(out.cpu().double(), _linear_attention_ref(qkv, B, L, heads, dh, dh ** -0.5), rtol=2e-5, atol=2e-5)
+
+
+@pytest.mark.parametrize("B,L,heads,dh,code", [(1, 1025, 1, 8, EINVAL), (1, 8, 1, 65, EINVAL), (1, 1024, 1, 64, "failed with code -2")])
+def test_linear_attention_refuses(B, L, heads, dh, code):
+    """L > 1024 and dim_head > 64 are CDX_EINVAL; q, k, v of one head past 160 KiB of LDS is CDX_ELDS.  Nothing is launched."""
+    from cleandiffuser_amd.engine import blocks
+    qkv = torch.zeros(B * L, 3 * heads * dh, device=DEV)
+    out = torch.full((B * L, heads * dh), 7.0, device=DEV)
+    with pytest.raises(RuntimeError, match=code):
+        blocks.linear_attention(qkv, B, L, heads, dh, out=out)
+    torch.cuda.synchronize()
+    assert (out == 7.0).all()
+
+
+def test_linear_attention_empty_batch():
+    from cleandiffuser_amd.engine import blocks
+    out = blocks.linear_attention(torch.empty(0, 3 * 2 * 8, device=DEV), 0, 5, 2, 8)
+    torch.cuda.synchronize()
+    assert out.shape == (0, 16)
+
+
 @pytest.mark.parametrize("tokens,n_obs,heads,dh,per_sample", [(16, 2, 4, 64, False), (12, 3, 4, 16, True), (5, 0, 2, 8, False),
                                                               (16, 15, 2, 4, False), (7, 2, 3, 6, True), (3, 1, 1, 256, False),
                                                               (33, 4, 5, 128, True), (1, 0, 7, 32, False)])
