@@ -14,6 +14,7 @@
 
 #include "../../include/cdx.h"
 #include "cdx_ops2.h"
+#include "cdx_step.h"
 
 extern void cdx_set_err(const char* msg);
 
@@ -75,8 +76,8 @@ __global__ void mlp_features_kernel(float* __restrict__ out, const float* __rest
 }
 
 // ------------------------------------------------------------------------------------------------
-// One solver step on a chunk, state in HBM: guidance combine, clip, eps/x0 conversion, update, fix-mask blend.
-// Same arithmetic, in the same order, as the in-LDS step of cdx_unet2.hip (kinds 0-4); kinds 5/6 are EDM.
+// One solver step on a chunk, state in HBM: guidance combine and gradient shift here, then cdx_step_element() (cdx_step.h, kinds 0-7):
+// clip, eps/x0 conversion, update, fix-mask blend.
 // ------------------------------------------------------------------------------------------------
 struct StepArgs {
     float* x;             // (nb, hd) chunk state, in/out
@@ -95,82 +96,34 @@ struct StepArgs {
     float cg_scale;       // pred += cg_scale * grad before clipping (classifier guidance)
 };
 
+// what cdx_step_element() reads and writes of one element (i = l * hd + e) of a chunk
+struct StepIO {
+    const StepArgs& a;
+    size_t i;
+    int l, e;
+    __device__ bool has_min() const { return a.x_min != nullptr; }
+    __device__ bool has_max() const { return a.x_max != nullptr; }
+    __device__ bool has_mask() const { return a.fix_mask != nullptr; }
+    __device__ float x_min() const { return a.x_min[e]; }
+    __device__ float x_max() const { return a.x_max[e]; }
+    __device__ float mask() const { return a.fix_mask[e]; }
+    __device__ float prior() const { return a.prior[i]; }
+    __device__ float noise(int idx) const { return a.noise[((size_t)idx * a.batch + a.b0 + l) * a.hd + e]; }
+    __device__ float prev() const { return a.prev[i]; }
+    __device__ float xold() const { return a.xold[i]; }
+    __device__ void push(float v) const { a.prev[i] = v; }
+    __device__ void push_edm(float s, float x) const { a.prev[i] = s; a.xold[i] = x; }
+};
+
 __global__ void solver_step_kernel(const StepArgs a) {
     const size_t n = (size_t)a.nb * a.hd;
-    const cdx_step& st = a.st;
-    const float al = st.alpha, sg = st.sigma;
-    const float k0 = st.k[0], k1 = st.k[1], k2 = st.k[2], k3 = st.k[3], k4 = st.k[4];
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const int e = (int)(i % a.hd);
         const int l = (int)(i / a.hd);
-        const float x = a.x[i];
         float p = a.pred[i];
         if (a.cfg_mode == 2) p = a.cfg_w * p + (1.0f - a.cfg_w) * a.pred[n + i];
         if (a.grad) p += a.cg_scale * a.grad[i];
-        float xn;
-        if (st.kind >= 5) {  // EDM: p is the raw network output F
-            float d = k0 * x + k1 * p;
-            if (a.x_min) d = fmaxf(d, a.x_min[e]);
-            if (a.x_max) d = fminf(d, a.x_max[e]);
-            if (st.kind == 7) {                          // consistency model: x <- f(x) [mask], then re-noise for the next level
-                xn = d;
-                if (a.fix_mask) {
-                    const float m = a.fix_mask[e];
-                    xn = xn * (1.0f - m) + a.prior[i] * m;
-                }
-                if (st.noise_idx >= 0) xn += k3 * a.noise[((size_t)st.noise_idx * a.batch + a.b0 + l) * a.hd + e];
-                a.x[i] = xn;
-                continue;
-            }
-            float s = (x - d) / k2;
-            if (st.flags & CDX_STEP_MASK_PRED) s *= 1.0f - (a.fix_mask ? a.fix_mask[e] : 0.f);   // legacy EDM masks its slope (edm.py dot_x)
-            if (st.kind == 5) {
-                xn = x - s * k3;
-                if (st.push) { a.prev[i] = s; a.xold[i] = x; }
-            } else {
-                xn = a.xold[i] - (a.prev[i] + s) / 2.0f * k3;
-            }
-        } else {
-            if (a.predict_noise) {
-                if (a.x_max) p = fmaxf(p, (x - al * a.x_max[e]) / sg);
-                if (a.x_min) p = fminf(p, (x - al * a.x_min[e]) / sg);
-            } else {
-                if (a.x_min) p = fmaxf(p, a.x_min[e]);
-                if (a.x_max) p = fminf(p, a.x_max[e]);
-            }
-            float eps, xth;
-            if (a.predict_noise) { eps = p; xth = (x - sg * p) / al; }
-            else { xth = p; eps = (x - al * p) / sg; }
-            const size_t zi = ((size_t)(st.noise_idx < 0 ? 0 : st.noise_idx) * a.batch + a.b0 + l) * a.hd + e;
-            if (st.kind >= 3) {
-                const float m = a.fix_mask ? a.fix_mask[e] : 0.f;
-                if (st.kind == 3) { p = p * (1.0f - m); xn = k0 * (x - k1 * p); }
-                else { p = p * (1.0f - m) + x * m; xn = k0 * (k1 * x + k2 * p); }
-                if (st.noise_idx >= 0) xn += k3 * a.noise[zi];
-            } else if (st.kind == 0) {
-                xn = k0 * (x - k1 * eps) + k2 * eps;
-                if (st.noise_idx >= 0) xn += k3 * a.noise[zi];
-            } else if (st.kind == 1) {
-                xn = k0 * ((x - k1 * eps) / k2) + k3 * eps;
-            } else {
-                if (st.flags & CDX_STEP_MASK_PRED) {
-                    const float m = a.fix_mask ? a.fix_mask[e] : 0.f;
-                    eps = eps * (1.0f - m);
-                    xth = xth * (1.0f - m) + x * m;
-                }
-                float v = (st.vsel & 1) ? xth : eps;
-                if (st.vsel == 2) v = k3 * xth - k4 * a.prev[i];
-                if (st.vsel == 3) v = k3 * eps - k4 * a.prev[i];
-                xn = k0 * x - k1 * v;
-                if (st.noise_idx >= 0) xn += k2 * a.noise[zi];
-            }
-            if (st.push) a.prev[i] = st.push == 2 ? eps : xth;
-        }
-        if (a.fix_mask) {
-            const float m = a.fix_mask[e];
-            xn = xn * (1.0f - m) + a.prior[i] * m;
-        }
-        a.x[i] = xn;
+        a.x[i] = cdx_step_element<true>(a.st, a.predict_noise, a.x[i], p, StepIO{a, i, l, e});
     }
 }
 

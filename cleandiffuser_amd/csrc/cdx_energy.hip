@@ -16,7 +16,7 @@
 //      with the hidden pre-activations kept in LDS, then g = d logp.sum() / d x_s as engine/mlp_grad.py does it: x SiLU'(pre), the
 //      transposed weights, then through act_proj.  obs_proj(obs) does not depend on the step: once per tile before the loop.  The
 //      classifier's images alias the denoiser's (the prediction is in its own tile by then);
-//   3. pred += cg_scale[s] g, clip, eps <-> x0, the affine update, + k z, fix-mask blend: cdx_rollout_fwd_kernel's solver step.
+//   3. pred += cg_scale[s] g, then cdx_step_element() (cdx_step.h): clip, eps <-> x0, the affine update, + k z, fix-mask blend.
 // After the last step one more energy forward on the unclipped x_S with clf_temb[S] (t = 0) gives logp_out.  No atomics, every element
 // is produced by one fixed lane in one fixed order: bit-reproducible.
 #include <hip/hip_runtime.h>
@@ -36,8 +36,8 @@ constexpr int EN_ALD = 68;       // row stride of the state tile (an MFMA A oper
 constexpr long long EN_LDS_MAX = 160 * 1024;
 
 struct EnStep {
-    int32_t kind, vsel, noise_idx;
-    float alpha, sigma, k0, k1, k2, k3, cg;
+    RowStep s;
+    float cg;              // cg_scale of the step
 };
 
 // the LDS plan, in floats.  [0, region) is shared by the two nets: the denoiser has three activation images [16][ld] and the skip stack
@@ -237,43 +237,14 @@ __global__ __launch_bounds__(256) void cdx_energy_kernel(const EnArgs a) {
         // ---- 2. energy model: logp and its gradient at x_s ----
         clf_backward(clf_forward(g.clf_temb + (size_t)s * Ec));
         if (g.trace_logp != nullptr && tid < RO_ROWS && row0 + tid < B) g.trace_logp[(size_t)s * B + row0 + tid] = lp[tid];
-        // ---- 3. shift and solver step (the solver step of cdx_rollout_fwd_kernel) ----
-        const float al = st.alpha, sg = st.sigma, k0 = st.k0, k1 = st.k1, k2 = st.k2, k3 = st.k3;
+        // ---- 3. shift and solver step (cdx_step.h; kinds 0-2 without memory, by en_check) ----
+        const cdx_step rec = st.s.record();
         for (int i = tid; i < RO_ROWS * A; i += 256) {
             const int rr = i / A, e = i - rr * A, row = row0 + rr;
-            const float x = xs[rr * EN_ALD + e];
             const float gv = gr[rr * EN_XLD + e];
             if (g.trace_grad != nullptr && row < B) g.trace_grad[((size_t)s * B + row) * A + e] = gv;
-            float pv = pr[rr * EN_XLD + e] + st.cg * gv;
-            if (g.clip) {
-                if (g.predict_noise) {
-                    if (g.x_max) pv = fmaxf(pv, (x - al * g.x_max[e]) / sg);
-                    if (g.x_min) pv = fminf(pv, (x - al * g.x_min[e]) / sg);
-                } else {
-                    if (g.x_min) pv = fmaxf(pv, g.x_min[e]);
-                    if (g.x_max) pv = fminf(pv, g.x_max[e]);
-                }
-            }
-            float eps, xth;
-            if (g.predict_noise) { eps = pv; xth = (x - sg * pv) / al; }
-            else { xth = pv; eps = (x - al * pv) / sg; }
-            const float z = (st.noise_idx >= 0 && row < B) ? g.noise[((size_t)st.noise_idx * B + row) * A + e] : 0.f;
-            float xn;
-            if (st.kind == 0) {
-                xn = k0 * (x - k1 * eps) + k2 * eps;
-                if (st.noise_idx >= 0) xn += k3 * z;
-            } else if (st.kind == 1) {
-                xn = k0 * ((x - k1 * eps) / k2) + k3 * eps;
-            } else {
-                const float v = (st.vsel & 1) ? xth : eps;
-                xn = k0 * x - k1 * v;
-                if (st.noise_idx >= 0) xn += k2 * z;
-            }
-            if (g.fix_mask) {
-                const float m = g.fix_mask[e];
-                xn = xn * (1.0f - m) + (row < B ? g.prior[(size_t)row * A + e] : 0.f) * m;
-            }
-            xs[rr * EN_ALD + e] = xn;
+            const RowStepIO io{g.clip ? g.x_min : nullptr, g.clip ? g.x_max : nullptr, g.fix_mask, g.prior, g.noise, B, A, row, e};
+            xs[rr * EN_ALD + e] = cdx_step_element<false>(rec, g.predict_noise, xs[rr * EN_ALD + e], pr[rr * EN_XLD + e] + st.cg * gv, io);
         }
         __syncthreads();
     }
@@ -411,11 +382,8 @@ int cdx_energy_guided_run(const cdx_energy_guided* g, void* hip_stream) {
     a.g.steps = nullptr;
     a.g.cg_scale = nullptr;
     for (int i = 0; i < CDX_ENERGY_MAX_BLOCKS; ++i) a.blk[i] = g->blocks[i < g->n_blocks ? i : 0];
-    for (int i = 0; i < g->S; ++i) {
-        const cdx_step& st = g->steps[i];
-        a.st[i] = EnStep{st.kind, st.vsel, st.noise_idx, st.alpha, st.sigma, st.k[0], st.k[1], st.k[2], st.k[3], g->cg_scale[i]};
-    }
-    for (int i = g->S; i < CDX_ENERGY_MAX_STEPS; ++i) a.st[i] = EnStep{0, 0, -1, 1.f, 1.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < g->S; ++i) a.st[i] = EnStep{RowStep::of(g->steps[i]), g->cg_scale[i]};
+    for (int i = g->S; i < CDX_ENERGY_MAX_STEPS; ++i) a.st[i] = EnStep{RowStep{0, 0, -1, 1.f, 1.f, 0.f, 0.f, 0.f, 0.f}, 0.f};
     const size_t lds = (size_t)a.p.total * sizeof(float);
     static size_t raised = 0;
     if (lds > 48 * 1024 && lds > raised) {

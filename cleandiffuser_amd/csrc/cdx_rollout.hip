@@ -13,8 +13,8 @@
 //     lane), G_head[s], g_cond (summed over the steps in LDS: row-local) and g_temb as (B, S*E) rows -- one cdx_colsum_f32 over the B rows
 //     gives (S*E).  No atomics anywhere: both kernels are bit-reproducible.
 // The weight / bias sums over the batch are NOT done here: dW_l = sum_s G[l][s]^T H[l-1][s] is one cdx_conv_wgrad_f32 product per layer
-// over the S*B rows (engine/rollout.py).  The solver arithmetic is that of solver_step_kernel (cdx_bigbatch.hip), kinds 0 / 1 / 2 with
-// vsel 0 / 1, in the same order, so the values agree with the no-grad one-launch path.
+// over the S*B rows (engine/rollout.py).  The solver step is cdx_step_element() (cdx_step.h), the one every sampling kernel runs, on
+// kinds 0 / 1 / 2 with vsel 0 / 1, so the values agree with the no-grad one-launch path.
 //
 // Saved activations are laid out (3, S, B, W) -- layer-major -- so that the S*B rows of one layer are ONE row-major matrix.
 #include <hip/hip_runtime.h>
@@ -32,11 +32,10 @@ namespace {
 constexpr int RO_XLD = 64;       // row stride of the (16 x A) state / gradient tiles (A <= 64)
 constexpr int RO_GLD = 68;       // row stride of the head-gradient tile (an MFMA A operand: padded against bank conflicts)
 
-// what a kernel needs of a cdx_step, plus the two derivatives of the update the backward pass uses:
+// the step record, plus the two derivatives of the update the backward pass uses:
 //   x' = cx * x + cp * P (+ noise)   with P the CLIPPED prediction (d x'/d x at fixed P, d x'/d P)
 struct RoStep {
-    int32_t kind, vsel, noise_idx;
-    float alpha, sigma, k0, k1, k2, k3;
+    RowStep s;
     float cx, cp;
 };
 
@@ -118,40 +117,12 @@ __global__ __launch_bounds__(256) void cdx_rollout_fwd_kernel(const RoArgs a) {
             if (row < B) r.P_raw[((size_t)s * B + row) * A + n] = p;
         });
         __syncthreads();
-        // solver step (solver_step_kernel of cdx_bigbatch.hip, kinds 0-2)
-        const float al = st.alpha, sg = st.sigma, k0 = st.k0, k1 = st.k1, k2 = st.k2, k3 = st.k3;
+        // solver step (cdx_step.h; kinds 0-2 without memory, by ro_check)
+        const cdx_step rec = st.s.record();
         for (int i = tid; i < RO_ROWS * A; i += 256) {
             const int rr = i / A, e = i - rr * A, row = row0 + rr;
-            const float x = xs[rr * RO_XLD + e];
-            float p = pr[rr * RO_XLD + e];
-            if (r.clip) {
-                if (r.predict_noise) {
-                    if (r.x_max) p = fmaxf(p, (x - al * r.x_max[e]) / sg);
-                    if (r.x_min) p = fminf(p, (x - al * r.x_min[e]) / sg);
-                } else {
-                    if (r.x_min) p = fmaxf(p, r.x_min[e]);
-                    if (r.x_max) p = fminf(p, r.x_max[e]);
-                }
-            }
-            float eps, xth;
-            if (r.predict_noise) { eps = p; xth = (x - sg * p) / al; }
-            else { xth = p; eps = (x - al * p) / sg; }
-            const float z = (st.noise_idx >= 0 && row < B) ? r.noise[((size_t)st.noise_idx * B + row) * A + e] : 0.f;
-            float xn;
-            if (st.kind == 0) {
-                xn = k0 * (x - k1 * eps) + k2 * eps;
-                if (st.noise_idx >= 0) xn += k3 * z;
-            } else if (st.kind == 1) {
-                xn = k0 * ((x - k1 * eps) / k2) + k3 * eps;
-            } else {
-                const float v = (st.vsel & 1) ? xth : eps;
-                xn = k0 * x - k1 * v;
-                if (st.noise_idx >= 0) xn += k2 * z;
-            }
-            if (r.fix_mask) {
-                const float m = r.fix_mask[e];
-                xn = xn * (1.0f - m) + (row < B ? r.prior[(size_t)row * A + e] : 0.f) * m;
-            }
+            const RowStepIO io{r.clip ? r.x_min : nullptr, r.clip ? r.x_max : nullptr, r.fix_mask, r.prior, r.noise, B, A, row, e};
+            const float xn = cdx_step_element<false>(rec, r.predict_noise, xs[rr * RO_XLD + e], pr[rr * RO_XLD + e], io);
             xs[rr * RO_XLD + e] = xn;
             if (row < B) r.X[((size_t)(s + 1) * B + row) * A + e] = xn;
         }
@@ -188,7 +159,7 @@ __global__ __launch_bounds__(256) void cdx_rollout_bwd_kernel(const RoArgs a) {
 
     for (int s = S - 1; s >= 0; --s) {
         const RoStep& st = a.st[s];
-        const float al = st.alpha, sg = st.sigma;
+        const float al = st.s.alpha, sg = st.s.sigma;
         // blend, update, conversion and clamp: d loss / d P_raw and the direct part of d loss / d x_s
         for (int i = tid; i < RO_ROWS * RO_XLD; i += 256) {
             const int rr = i / RO_XLD, e = i - rr * RO_XLD, row = row0 + rr;
@@ -309,9 +280,7 @@ void ro_pack(const cdx_rollout* r, RoArgs* a) {
     for (int i = 0; i < r->S; ++i) {
         const cdx_step& st = r->steps[i];
         RoStep& o = a->st[i];
-        o.kind = st.kind; o.vsel = st.vsel; o.noise_idx = st.noise_idx;
-        o.alpha = st.alpha; o.sigma = st.sigma;
-        o.k0 = st.k[0]; o.k1 = st.k[1]; o.k2 = st.k[2]; o.k3 = st.k[3];
+        o.s = RowStep::of(st);
         // x' = ax * x + ae * eps + at * xth, with eps = ex * x + ep * P and xth = tx * x + tp * P
         const double al = st.alpha, sg = st.sigma, k0 = st.k[0], k1 = st.k[1], k2 = st.k[2], k3 = st.k[3];
         const double ex = r->predict_noise ? 0.0 : 1.0 / sg, ep = r->predict_noise ? 1.0 : -al / sg;

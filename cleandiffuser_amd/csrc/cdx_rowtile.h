@@ -1,9 +1,12 @@
 // cdx_rowtile.h -- the product routine of the row-tile kernels (cdx_rollout.hip, cdx_energy.hip): one workgroup of 4 wave64 owns 16 rows,
 // activations live in LDS, weights are read from global memory (L2-resident, the same for every workgroup), products run on
-// v_mfma_f32_16x16x4_f32 (exact fp32, rows on the M axis; lane maps: cdx_probe_mfma_layout).
+// v_mfma_f32_16x16x4_f32 (exact fp32, rows on the M axis; lane maps: cdx_probe_mfma_layout); and what both need to run the solver step
+// of cdx_step.h on their (16 x A) state tile.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "cdx_step.h"
 
 namespace {
 
@@ -75,5 +78,35 @@ __device__ __forceinline__ void ro_product(const float* in, int ld, const float*
         }
     }
 }
+
+// what a row-tile kernel carries of a cdx_step in its argument block (the entry points admit kinds 0-2 with vsel <= 1 and no flags:
+// no multistep memory, no push, k[4] unused)
+struct RowStep {
+    int32_t kind, vsel, noise_idx;
+    float alpha, sigma, k0, k1, k2, k3;
+    static RowStep of(const cdx_step& st) {
+        return RowStep{st.kind, st.vsel, st.noise_idx, st.alpha, st.sigma, st.k[0], st.k[1], st.k[2], st.k[3]};
+    }
+    __device__ cdx_step record() const { return cdx_step{kind, vsel, noise_idx, 0, alpha, sigma, {k0, k1, k2, k3, 0.f}, 0}; }
+};
+
+// cdx_step_element()'s view of element e of batch row `row`: bounds and mask (A), prior (B, A) and noise (n_noise, B, A) in global
+// memory; rows of the tile past the batch read noise and prior as 0
+struct RowStepIO {
+    const float *lo, *hi, *fix_mask, *prior_rows, *noise_rows;
+    int B, A, row, e;
+    __device__ bool has_min() const { return lo != nullptr; }
+    __device__ bool has_max() const { return hi != nullptr; }
+    __device__ bool has_mask() const { return fix_mask != nullptr; }
+    __device__ float x_min() const { return lo[e]; }
+    __device__ float x_max() const { return hi[e]; }
+    __device__ float mask() const { return fix_mask[e]; }
+    __device__ float prior() const { return row < B ? prior_rows[(size_t)row * A + e] : 0.f; }
+    __device__ float noise(int idx) const { return row < B ? noise_rows[((size_t)idx * B + row) * A + e] : 0.f; }
+    __device__ float prev() const { return 0.f; }
+    __device__ float xold() const { return 0.f; }
+    __device__ void push(float) const {}
+    __device__ void push_edm(float, float) const {}
+};
 
 }  // namespace

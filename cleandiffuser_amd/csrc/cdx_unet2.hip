@@ -33,6 +33,7 @@
 #include "../../include/cdx.h"
 #include "cdx_act.h"
 #include "cdx_ops2.h"
+#include "cdx_step.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 // Descriptor / item words are read through the constant address space: a wave-uniform address there is an s_load (scalar
@@ -1447,13 +1448,36 @@ __global__ __launch_bounds__(NWV * 64, (NWV == 8 || T == 1) ? 2 : 1) void cdx_un
         // v_readlane on the critical path of every op).
         const KArg* S = kernarg();
         asm volatile("" : "+s"(S));
-        // ---- clip, eps/x0 conversion, solver update, fix-mask blend on the LDS-resident state (kinds 0-4) ----
+        // ---- the solver step on the LDS-resident state: cdx_step_element() of cdx_step.h (kinds 0-4; COND programs: 0-7) ----
         const cdx_step st = S->steps[step];
-        const float al = st.alpha, sg = st.sigma;
-        const float k0 = st.k[0], k1 = st.k[1], k2 = st.k[2], k3 = st.k[3], k4 = st.k[4];
         const bool edm = COND && st.kind >= 5;
         const bool xglob = S->compact || edm;                  // the authoritative state lives in x_out, memory in the ws block
         const float c_next = (edm && step + 1 < S->n_steps) ? S->steps[step + 1].alpha : 1.0f;   // the NEXT forward sees c_in * x
+        // where the step's operands live; addresses are formed inside the methods, from the kernarg pointer, only where a record needs
+        // them.  Memory: EDM plans keep [slope | x_old] in the trajectory's ws block, compact programs the multistep memory at the head
+        // of the same block, every other program in the LDS slot prev_off.
+        struct StepIO {
+            const KArg* S;
+            float *tl, *wsb;
+            size_t xbase;
+            int e, b, HD, HDp;
+            bool edm;
+            __device__ bool has_min() const { return S->x_min != nullptr; }
+            __device__ bool has_max() const { return S->x_max != nullptr; }
+            __device__ bool has_mask() const { return S->fix_mask != nullptr; }
+            __device__ float x_min() const { return S->x_min[e]; }
+            __device__ float x_max() const { return S->x_max[e]; }
+            __device__ float mask() const { return S->fix_mask[e]; }
+            __device__ float prior() const { return S->prior[xbase + e]; }
+            __device__ float noise(int idx) const { return S->noise[((size_t)idx * S->batch + b) * HD + e]; }
+            __device__ float prev() const { return edm ? wsb[e] : S->compact ? S->ws[(size_t)b * S->ws_floats + e] : tl[S->prev_off + e]; }
+            __device__ float xold() const { return wsb[HDp + e]; }
+            __device__ void push(float v) const {
+                if (S->compact) S->ws[(size_t)b * S->ws_floats + e] = v;
+                else tl[S->prev_off + e] = v;
+            }
+            __device__ void push_edm(float sl, float x) const { wsb[e] = sl; wsb[HDp + e] = x; }
+        };
 #pragma unroll 1
         for (int t = 0; t < T; ++t) {
             if (b0 + t >= b_end) break;
@@ -1468,90 +1492,12 @@ __global__ __launch_bounds__(NWV * 64, (NWV == 8 || T == 1) ? 2 : 1) void cdx_un
                 const float x = xglob ? S->x_out[xbase + e] : tl[xo];
                 float p = tl[S->pred_off + n * S->pred_stride + c];
                 if (COND && n_pass == 2) p = S->cfg_w * wsb[2 * HDp + e] + (1.0f - S->cfg_w) * p;   // w * cond + (1 - w) * uncond
-                if (edm) {
-                    // EDM (reference newedm.py:387-401, legacy edm.py:118-160): D = clip(c_skip x + c_out F), slope = (x - D) / sigma;
-                    // kind 7 = consistency model (consistency_model.py:412-427): x <- f(x) [mask], then re-noise for the next level
-                    float dn = k0 * x + k1 * p, xe;
-                    if (S->x_min) dn = fmaxf(dn, S->x_min[e]);
-                    if (S->x_max) dn = fminf(dn, S->x_max[e]);
-                    if (st.kind == 7) {
-                        xe = dn;
-                        if (S->fix_mask) {
-                            const float m = S->fix_mask[e];
-                            xe = xe * (1.0f - m) + S->prior[xbase + e] * m;
-                        }
-                        if (st.noise_idx >= 0) xe += k3 * S->noise[((size_t)st.noise_idx * S->batch + b) * HD + e];
-                    } else {
-                        const float sl = (x - dn) / k2;
-                        if (st.kind == 5) {
-                            xe = x - sl * k3;
-                            if (st.push) { wsb[e] = sl; wsb[HDp + e] = x; }
-                        } else {
-                            xe = wsb[HDp + e] - (wsb[e] + sl) / 2.0f * k3;
-                        }
-                        if (S->fix_mask) {
-                            const float m = S->fix_mask[e];
-                            xe = xe * (1.0f - m) + S->prior[xbase + e] * m;
-                        }
-                    }
-                    tl[xo] = c_next * xe;
-                    S->x_out[xbase + e] = xe;
-                    continue;
-                }
                 // classifier guidance (reference diffusionsde.py:153-173): the prediction is shifted along d log p / d x_t BEFORE
                 // it is clipped; cg_scale[step] = -w sigma (noise prediction) or w sigma^2 / alpha (x0 prediction), frozen by the host
-                if (BWD && S->cg_scale) p += S->cg_scale[step] * tl[S->grad_off + n * S->grad_stride + c];
-                if (S->predict_noise) {
-                    if (S->x_max) p = fmaxf(p, (x - al * S->x_max[e]) / sg);
-                    if (S->x_min) p = fminf(p, (x - al * S->x_min[e]) / sg);
-                } else {
-                    if (S->x_min) p = fmaxf(p, S->x_min[e]);
-                    if (S->x_max) p = fminf(p, S->x_max[e]);
-                }
-                float eps, xth, xn;
-                if (S->predict_noise) {
-                    eps = p; xth = (x - sg * p) / al;
-                } else {
-                    xth = p; eps = (x - al * p) / sg;
-                }
-                if (st.kind >= 3) {
-                    // legacy DDPM class (reference diffusion/ddpm.py:153-164, 230-241): fix-mask on the prediction
-                    const float m = S->fix_mask ? S->fix_mask[e] : 0.f;
-                    if (st.kind == 3) {
-                        p = p * (1.0f - m);
-                        xn = k0 * (x - k1 * p);
-                    } else {
-                        p = p * (1.0f - m) + x * m;
-                        xn = k0 * (k1 * x + k2 * p);
-                    }
-                    if (st.noise_idx >= 0) xn += k3 * S->noise[((size_t)st.noise_idx * S->batch + b) * HD + e];
-                } else if (st.kind == 0) {
-                    xn = k0 * (x - k1 * eps) + k2 * eps;
-                    if (st.noise_idx >= 0) xn += k3 * S->noise[((size_t)st.noise_idx * S->batch + b) * HD + e];
-                } else if (st.kind == 1) {
-                    xn = k0 * ((x - k1 * eps) / k2) + k3 * eps;
-                } else {
-                    if (st.flags & CDX_STEP_MASK_PRED) {     // legacy DPMSolver (dpmsolver.py:257-264)
-                        const float m = S->fix_mask ? S->fix_mask[e] : 0.f;
-                        eps = eps * (1.0f - m);
-                        xth = xth * (1.0f - m) + x * m;
-                    }
-                    float v = (st.vsel & 1) ? xth : eps;
-                    if (st.vsel == 2) v = k3 * xth - k4 * (S->compact ? S->ws[(size_t)b * S->ws_floats + e] : tl[S->prev_off + e]);
-                    if (st.vsel == 3) v = k3 * eps - k4 * (S->compact ? S->ws[(size_t)b * S->ws_floats + e] : tl[S->prev_off + e]);
-                    xn = k0 * x - k1 * v;
-                    if (st.noise_idx >= 0) xn += k2 * S->noise[((size_t)st.noise_idx * S->batch + b) * HD + e];
-                }
-                if (S->fix_mask) {
-                    const float m = S->fix_mask[e];
-                    xn = xn * (1.0f - m) + S->prior[xbase + e] * m;
-                }
-                if (st.push) {
-                    if (S->compact) S->ws[(size_t)b * S->ws_floats + e] = st.push == 2 ? eps : xth;
-                    else tl[S->prev_off + e] = st.push == 2 ? eps : xth;
-                }
-                tl[xo] = xn;
-                if (S->compact) S->x_out[xbase + e] = xn;
+                if (BWD && !edm && S->cg_scale) p += S->cg_scale[step] * tl[S->grad_off + n * S->grad_stride + c];
+                const float xn = cdx_step_element<COND>(st, S->predict_noise, x, p, StepIO{S, tl, wsb, xbase, e, b, HD, HDp, edm});
+                tl[xo] = c_next * xn;
+                if (xglob) S->x_out[xbase + e] = xn;
             }
             if (S->compact) {
                 // the LDS state slot of a compact program is an arena slot: other tensors lived there during the forward, so its halo

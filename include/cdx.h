@@ -38,11 +38,11 @@ extern "C" {
  *            `alpha` carries c_in (the network sees c_in*x), k = (c_skip, c_out, sigma, dt):
  *            D = clip(k0*x + k1*F); s = (x - D)/k2;  kind 5: x' = x - k3*s (push: remember s and x);
  *            kind 6: x' = x_old - k3*(s_old + s)/2.  With CDX_STEP_MASK_PRED (legacy EDM class, edm.py:118-160: the slope is
- *            masked) s <- s*(1-mask) first -- cdx_bigbatch.hip; the in-LDS step of cdx_unet2.hip leaves s as it is, which gives the
- *            same x' wherever the mask is 0 or 1.
+ *            masked) s <- s*(1-mask) first.
  *   kind 7 (consistency model, reference diffusion/consistency_model.py:412-427): x' = mask(D) [+ k3*z]  (re-noising for
  *            the next level; the fix-mask is applied BEFORE the noise).   A plan is all-EDM-family (5/6/7) or not at all.
- * followed by the fix-mask blend (diffusionsde.py:592). */
+ * followed by the fix-mask blend (diffusionsde.py:592).  Every sampling kernel applies a record through the one function of
+ * csrc/cdx_step.h. */
 #define CDX_STEP_MASK_PRED 1
 typedef struct cdx_step {
     int32_t kind;        /* 0 ddpm, 1 ddim, 2 linear, 3 legacy-ddpm eps, 4 legacy-ddpm x0, 5 edm euler, 6 edm heun, 7 consistency */

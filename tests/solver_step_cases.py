@@ -12,7 +12,8 @@ kernel and the plan builders' record forms (engine/plan.py); tests/test_solver_s
 that set, so a new branch needs a case and a case that stops reaching its branch fails.
 
 Every case samples a tiny IDQLMlp (the residual-MLP executor, ``cdx_resmlp_run``); ``EXECUTORS`` has the smallest nets of the other
-four executors for the subset of ``EXECUTOR_SUBSET``.  Weights are ``load_synth`` streams with the output layer scaled by `den_scale`;
+four executors for the subset of ``EXECUTOR_SUBSET``, and a JannerUNet1d: the two U-Nets also run ``PROGRAM_SUBSET`` on the program
+kernel, which calls the same step function (csrc/cdx_step.h).  Weights are ``load_synth`` streams with the output layer scaled by `den_scale`;
 bounds, `den_scale` and `temperature` are chosen per family so that the float64 run ALONE meets the conditions of the CPU test (a clamp
 that changes between 2 % and 60 % of the elements at some step, a visible classifier-free difference)."""
 import contextlib
@@ -191,6 +192,7 @@ EXECUTORS = {       # name -> net, state shape, condition shape, the name bigbat
     "pearcetf": _e(("PearceTransformer", dict(act_dim=5, To=2, emb_dim=16, trans_emb_dim=16, nhead=2)), (5,), (2, 16), "pearcetf", True),
     "chiunet": _e(("ChiUNet1d", dict(act_dim=3, obs_dim=OBS, To=2, model_dim=16, emb_dim=16, dim_mult=[1, 2], kernel_size=3)), (4, 3),
                   (2, OBS), "chiunet", True),
+    "janner": _e(("JannerUNet1d", dict(in_dim=3, model_dim=16, emb_dim=16, dim_mult=[1, 2], kernel_size=3)), (4, 3), (16,), "chiunet"),
 }
 # `prev` / `xold` / `pred` are each executor's own buffers: a 2M multistep with cfg_mode 2, EDM Heun with clamp and mask, consistency with
 # mask and noise, legacy DDPM with mask (both predictions: of the GEMM executors only the U-Net one is offered the legacy DDPM class, so
@@ -202,6 +204,16 @@ _LEGACY_DDPM = ("dispatch.try_fused_legacy_ddpm offers the legacy DDPM class to 
 # (executor, case) -> reason: requests the dispatcher does not hand to the executor; they run the PyTorch loop and must still match
 REFUSED = {(ex, name): _LEGACY_DDPM for ex in ("mlp", "dit", "chitf", "pearcetf")
            for name in TABLE if CASES[name].cls == "DDPM" and (ex == "mlp" or name in EXECUTOR_SUBSET)}
+
+# The program kernel (csrc/cdx_unet2.hip) runs the same per-element step (csrc/cdx_step.h) on its LDS-resident state: the two U-Nets at
+# batch B, below their crossover to the GEMM executor, are served by runtime2.fused_sample2.  Beside EXECUTOR_SUBSET: the legacy EDM
+# class with a fix-mask (CDX_STEP_MASK_PRED on kinds 5 / 6: the slope is masked, which only the mask element of 0.5 can show), and a ddim
+# plan (kind 1, which no case of EXECUTOR_SUBSET has)
+PROGRAM_EXECUTORS = ("chiunet", "janner")
+PROGRAM_LEDM = ("ledm_heun_full", "ledm_euler_full", "ledm_heun_mask")
+PROGRAM_SUBSET = EXECUTOR_SUBSET + PROGRAM_LEDM + ("c_ddim_eps_full",)
+# (executor, case) -> reason: requests the dispatcher does not hand to the program kernel; they must still match on the route they take
+PROGRAM_REFUSED = {}
 
 
 def case_of(name, executor="mlp"):
@@ -282,6 +294,7 @@ def spied(net, seen):
         def spy(solver, model, plan, xt, prior, cond_vec, w_cfg, *a, **k):
             seen.plan, seen.xt = plan, xt.detach().clone()
             seen.cfg2 = cond_vec is not None and w_cfg not in (0.0, 1.0)
+            seen.cond, seen.w_cfg = cond_vec, w_cfg
             return orig[n](solver, model, plan, xt, prior, cond_vec, w_cfg, *a, **k)
         return spy
 
@@ -314,7 +327,7 @@ def host_run(name, dtype, executor="mlp", inp=None, case=None):
     case = case or case_of(name, executor)
     inp = make_inputs(name, executor) if inp is None else inp
     agent = build(name, executor, "cpu", dtype, case)
-    seen = SimpleNamespace(plan=None, xt=None, cfg2=False, share=[], halves=[], shape=inp["prior"].shape)
+    seen = SimpleNamespace(plan=None, xt=None, cfg2=False, cond=None, w_cfg=0.0, share=[], halves=[], shape=inp["prior"].shape)
     with spied(agent.model_ema["diffusion"], seen):
         x = sample(agent, case, inp, dtype=dtype)
     clamp = bool(getattr(seen.plan, "clip_each_step", True)) and (getattr(agent, "x_min", None) is not None or
@@ -322,7 +335,7 @@ def host_run(name, dtype, executor="mlp", inp=None, case=None):
     pn = _predicts_noise(seen.plan, agent)
     env = (int(clamp), int(torch.is_tensor(agent.fix_mask)), int(seen.cfg2))
     n_step_clips = len(seen.plan.steps) if clamp else 0
-    return SimpleNamespace(case=case, inp=inp, x=x, plan=seen.plan, xt=seen.xt, env=env,
+    return SimpleNamespace(case=case, inp=inp, x=x, plan=seen.plan, xt=seen.xt, env=env, cond=seen.cond, w_cfg=seen.w_cfg, predict_noise=pn,
                            signatures={normalise(st, pn) + env for st in seen.plan.steps},
                            step_share=seen.share[:n_step_clips], final_share=seen.share[n_step_clips:], halves=seen.halves,
                            fix_mask=agent.fix_mask[0] if torch.is_tensor(agent.fix_mask) else None)
@@ -333,6 +346,19 @@ def reference(name, executor="mlp"):
     """The float64 CPU run of case `name` with the net of `executor`: computed once per process and never modified."""
     return host_run(name, torch.float64, executor)
 
+
+def sim_run(name, executor, keep_flags=True):
+    """The plan of ``reference(name, executor)`` through ``oracle.step_sim.run_plan`` -- the record interpreter -- in float64 on the same
+    net, inputs and draws; `keep_flags` False clears every record's flags (CDX_STEP_MASK_PRED) first.  For cases without a clamp."""
+    import dataclasses
+    from oracle import step_sim
+    r = reference(name, executor)
+    assert r.env[0] == 0
+    net = build(name, executor, "cpu", torch.float64, r.case).model_ema["diffusion"]
+    plan = r.plan if keep_flags else dataclasses.replace(r.plan, steps=[dataclasses.replace(st, flags=0) for st in r.plan.steps])
+    t64 = lambda a: torch.from_numpy(np.asarray(a)).double()          # noqa: E731
+    return step_sim.run_plan(plan, net, r.xt, predict_noise=r.predict_noise, prior=t64(r.inp["prior"]),
+                             fix_mask=r.fix_mask, noise=list(t64(r.inp["noise"])[1:]), cond=r.cond, w_cfg=r.w_cfg)
 
 
 # ------------------------------------------------------------------------------------------------ #

@@ -15,7 +15,10 @@ EDM class masks its slope and the kernel did not.
 
 Every case runs on the residual-MLP executor, whole and in chunks of 2 (batch 5: the last chunk holds one row, so the `b0` offsets
 into noise, prior and the condition rows are exercised); a subset runs on the other four executors, whose prev / xold / pred buffers
-are their own; one case is large enough for a second trip of launch_step's grid-stride loop."""
+are their own; one case is large enough for a second trip of launch_step's grid-stride loop.
+
+The program kernel (csrc/cdx_unet2.hip) calls the same per-element step (csrc/cdx_step.h) on its LDS-resident state: the cases of
+``PROGRAM_SUBSET`` run on the two U-Nets at their default route, against the same references at the same tolerance."""
 import pytest
 import torch
 
@@ -85,6 +88,33 @@ def test_step_matches_float64_on_every_executor(executor, name, chunk, monkeypat
     assert ref.env[1] == 1 and (ref.env[2] == 1 or ref.case.cls == "ContinuousConsistencyModel")
     x = _run_case(name, executor, chunk, monkeypatch, ref)
     _check(x, ref.x, f"{executor} {name} chunk {chunk}")
+
+
+@pytest.mark.parametrize("name", S.PROGRAM_SUBSET)
+@pytest.mark.parametrize("executor", S.PROGRAM_EXECUTORS)
+def test_program_kernel_step_matches_float64(executor, name, monkeypatch):
+    """The same step (csrc/cdx_step.h) as the program kernel runs it on its LDS-resident state: batch 5 is below the U-Nets' crossover, so
+    with UNET_GEMM_MIN_BATCH left alone ``runtime2.fused_sample2`` serves the loop in one cdx_unet2_run launch.  The three masked ledm_*
+    cases are the ones a step that ignores CDX_STEP_MASK_PRED on kinds 5 / 6 fails (tests/test_solver_step_cases_cpu.py: by 0.1 and more
+    of the scale)."""
+    from cleandiffuser_amd.engine import runtime2
+    ref = S.reference(name, executor)
+    served, orig = [], runtime2.fused_sample2
+
+    def spy(*a, **k):
+        out = orig(*a, **k)
+        served.append(out is not None)
+        return out
+    monkeypatch.setattr(runtime2, "fused_sample2", spy)
+    calls = _spy_loops(monkeypatch)
+    x = S.sample(S.build(name, executor, DEV), ref.case, ref.inp, device=DEV)
+    torch.cuda.synchronize()
+    assert [c for c in calls if c[1] > 0] == [], "the GEMM executor ran the loop"
+    if (executor, name) in S.PROGRAM_REFUSED:
+        assert True not in served, "PROGRAM_REFUSED lists this request, but the program kernel served it"
+    else:
+        assert served == [True], f"exactly one program-kernel call must serve the loop, got {served}"
+    _check(x, ref.x, f"program {executor} {name}")
 
 
 def test_grid_stride_second_trip_matches_float64(monkeypatch):

@@ -94,6 +94,35 @@ def test_float64_run_meets_its_conditions(name, runs):
     assert bool(reads) == multistep, name
 
 
+def test_program_subset_reaches_every_kind_the_memory_read_and_both_pushes():
+    """What the program kernel's sweep (tests/test_gpu_solver_step.py) must reach of the shared step, on both of its executors."""
+    for executor in S.PROGRAM_EXECUTORS:
+        sigs = set().union(*(S.reference(name, executor).signatures for name in S.PROGRAM_SUBSET))
+        assert sigs <= S.SIGNATURES
+        assert {s[0] for s in sigs} == set(range(8)), executor
+        assert any(s[0] == 2 and s[1] == 2 for s in sigs), "a multistep read (vsel 2)"
+        assert any(s[0] == 2 and s[2] for s in sigs) and any(s[0] == 5 and s[2] for s in sigs), "the multistep push and the EDM push"
+        assert any(s[0] in (5, 6) and s[3] and s[7] for s in sigs), "CDX_STEP_MASK_PRED on an EDM record, with a fix-mask"
+
+
+@pytest.mark.parametrize("name", S.PROGRAM_LEDM)
+@pytest.mark.parametrize("executor", S.PROGRAM_EXECUTORS)
+def test_masked_legacy_edm_cases_show_a_step_that_ignores_the_flag(executor, name):
+    """The legacy EDM class masks its slope (CDX_STEP_MASK_PRED on kinds 5 / 6).  A step that ignores the flag -- the record interpreter
+    with the flags cleared -- must land far outside the GPU sweep's tolerance, or the sweep could not tell; with the flags it agrees with
+    the host loop.  Both relative to max(1, max |x64|), float64 throughout.  Measured, without / with the flags -- chiunet: ledm_heun_full
+    2.31e-1 / 2.0e-7, ledm_euler_full 2.31e-1 / 2.5e-8, ledm_heun_mask 1.05e-1 / 1.2e-7; janner: 3.52e-1 / 2.1e-7, 3.70e-1 / 1.7e-7,
+    3.79e-1 / 4.5e-7 (the bound of the first is 2.4e-3)."""
+    r = S.reference(name, executor)
+    assert r.env[1] == 1 and all(st.flags & 1 for st in r.plan.steps if st.kind in (5, 6))
+    scale = max(1.0, float(r.x.abs().max()))
+    off = float((S.sim_run(name, executor, keep_flags=False) - r.x).abs().max()) / scale
+    on = float((S.sim_run(name, executor) - r.x).abs().max()) / scale
+    print(f"\n{executor} {name}: flags cleared {off:.3e}, flags kept {on:.3e} of the scale {scale:.3f}")
+    assert off > 100 * 4.0 * S.YARDSTICK
+    assert on <= 1e-5
+
+
 @pytest.mark.parametrize("name", S.TABLE)
 def test_fp32_host_loop_is_within_the_yardstick(name, runs):
     r = runs[name]
