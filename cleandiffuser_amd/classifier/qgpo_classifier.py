@@ -21,6 +21,13 @@ class QGPOClassifier(BaseClassifier):
         return loss, stats
 
     def update(self, x: torch.Tensor, noise: torch.Tensor, y: Dict[str, torch.Tensor], update_ema: bool = True):
+        """One training step (reference classifier/qgpo_classifier.py:49-61).  On a ROCm device with the shipped network (SiLU MLP,
+        untrainable Fourier time embedding, K dividing 16, ``FusedAdam``) forward, loss and backward-data are one row-tile launch and the
+        whole step a handful (engine/cep.py); everything else runs the autograd body below."""
+        from ..engine import cep
+        log = cep.try_cep_update(self, x, noise, y, update_ema)
+        if log is not None:
+            return log
         loss, log = self.loss(x, noise, y)
         self.optim.zero_grad()
         loss.backward()

@@ -846,6 +846,53 @@ long long cdx_energy_guided_lds_bytes(const cdx_energy_guided* g);
 int cdx_energy_guided_run(const cdx_energy_guided* g, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * QGPO's contrastive energy training step in ONE launch (csrc/cdx_cep.hip).  A purely additive entry: no existing struct or call
+ * changes, so CDX_ABI_VERSION stays 18.  Reference: pipelines/qgpo_d4rl_mujoco.py:172-212 -- ``clf.update(noisy_act, t, {"soft_label",
+ * "obs"})`` of QGPOClassifier(QGPONNClassifier) (classifier/qgpo_classifier.py:16-61, nn_classifier/mlp.py:25-55) on B states x K
+ * support actions.  The R = B K rows are one row matrix: row r = state r / K, support action r % K.  One workgroup of 4 wave64 owns 16
+ * consecutive rows, i.e. 16 / K whole softmax groups (K must divide 16), and does forward, loss and backward-data for them:
+ *   forward   feat = [obs_proj(obs[b]) | act_proj(x[r]) | temb[b]] (R, 3 Ec), h_l = SiLU(W_l h_{l-1} + b_l), o = w_o . h + b_o,
+ *             f = 10 tanh(o / 10);
+ *   loss      per state b: lse = logsumexp_k f, stats[b] = { -sum_k y_bk (f_bk - lse), max_k f, min_k f, sum_k f }: one cdx_colsum_f32 over
+ *             the B rows gives B loss, B f_max, B f_min, B K f_mean;
+ *   backward  dL/df_bk = (softmax_k(f)_bk sum_j y_bj - y_bk) / B (the labels need not sum to 1), x (1 - tanh^2(o / 10)), through w_o, then
+ *             per hidden layer x SiLU'(pre) and the transposed product on the live weight, down to d / d feat.
+ * Written (caller-owned, nothing is allocated here): feat (R, 3 Ec); H, G LAYER-major -- layer l's (R, hidden[l]) row-major matrix starts at
+ * float R * (hidden[0] + .. + hidden[l-1]) --, H_l = SiLU(pre_l), G_l = dL/d pre_l; G_out (R) = dL/do; G_act (R, Ec) = the act_proj columns
+ * of d / d feat; G_obs (B, Ec) = its obs_proj columns summed over the K rows of the state (the time columns have no parameters behind
+ * them); stats (B, 4).  The weight / bias gradients are the caller's, one cdx_conv_wgrad_batch_f32 with db: (p, q, rows) = (G_l, H_{l-1} or
+ * feat, R) per hidden layer, (G_out, H_last, R) for the head, (G_act, x, R) for act_proj, (G_obs, obs, B) for obs_proj.
+ * Rows of the last tile past R carry a zero loss gradient and nothing is written for them.  Caller-owned memory, one kernel enqueued on
+ * `hip_stream`, no synchronisation, no allocation, capturable; no atomics, one fixed lane and order per element: bit-reproducible.
+ * Limits (CDX_EINVAL with a message, before anything is launched): K in {1, 2, 4, 8, 16}; every hidden width a multiple of 16 and <= 512;
+ * 1 <= n_hidden <= CDX_ENERGY_MAX_HIDDEN; A <= 64; Ec <= 128; O <= 512; no null weights or outputs; the LDS plan (cdx_cep_lds_bytes) at
+ * most 160 KiB.  B == 0 is CDX_OK.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct cdx_cep_step {
+    int32_t B, K, A, O, Ec;
+    int32_t n_hidden;          /* hidden layers of the mlp, 1 .. CDX_ENERGY_MAX_HIDDEN */
+    int32_t hidden[CDX_ENERGY_MAX_HIDDEN];              /* their widths */
+    const float* x;                                     /* (B K, A): the noisy support actions */
+    const float* obs;                                   /* (B, O) */
+    const float* temb;                                  /* (B, Ec): map_noise(t), one row per state */
+    const float* soft;                                  /* (B K): the soft labels */
+    const float *obs_w, *obs_b;                         /* (Ec, O), (Ec) */
+    const float *act_w, *act_b;                         /* (Ec, A), (Ec) */
+    const float* w[CDX_ENERGY_MAX_HIDDEN];              /* layer l: (hidden[l], l ? hidden[l-1] : 3 Ec): nn.Linear.weight as it lives */
+    const float* b[CDX_ENERGY_MAX_HIDDEN];              /* (hidden[l]) */
+    const float *wo, *bo;                               /* (1, hidden[n_hidden-1]), (1) */
+    float* feat;                                        /* (B K, 3 Ec) */
+    float *H, *G;                                       /* layer-major (see above) */
+    float* G_out;                                       /* (B K) */
+    float* G_act;                                       /* (B K, Ec) */
+    float* G_obs;                                       /* (B, Ec) */
+    float* stats;                                       /* (B, 4) */
+} cdx_cep_step;
+/* bytes of LDS one workgroup of this request needs, or a negative CDX_E* code when the sizes are out of range */
+long long cdx_cep_lds_bytes(const cdx_cep_step* g);
+int cdx_cep_step_f32(const cdx_cep_step* g, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimiser side of DiffusionModel.update(): multi-tensor AdamW + EMA + gradient-norm clipping.
  * Replaces, per update() call, torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW.step() + optimizer.zero_grad() +
  * DiffusionModel.ema_update() (reference diffusion/diffusionsde.py:114-141, diffusion/basic.py:66,83-86): one device table of
