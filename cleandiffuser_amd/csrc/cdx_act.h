@@ -1,6 +1,6 @@
 // cdx_act.h -- the per-element activation formulas of the library, one device function per CDX_ACT_* id (include/cdx.h) plus the Mish
-// derivative.  gm_act (cdx_gemm.hip), act2_f (cdx_unet2.hip) and the rollout kernels (cdx_rollout.hip) dispatch to these.  Two use sites
-// write their formula out instead (Mish in gm_act, GELU_ERF in act2_f): the same arithmetic, but through the call hipcc emits other
+// and SiLU derivatives.  gm_act (cdx_gemm.hip), act2_f (cdx_unet2.hip), the rollout kernels (cdx_rollout.hip) and the energy model of
+// the row-tile kernels (cdx_energy_mlp.h, cdx_energy.hip) dispatch to these.  Two use sites write their formula out instead (Mish in gm_act, GELU_ERF in act2_f): the same arithmetic, but through the call hipcc emits other
 // code for the kernels around them.  A change to a formula here goes to those two as well.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -32,6 +32,11 @@ __device__ __forceinline__ float cdx_act_gelu_erf(float x) {     // exact GELU
 }
 __device__ __forceinline__ float cdx_act_leaky(float x) { return x > 0.f ? x : 0.01f * x; }
 __device__ __forceinline__ float cdx_act_silu(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+// d/dx [x sigmoid(x)] = s (1 + x (1 - s)), s = sigmoid(x): the formula of cdx_act_bwd_f32
+__device__ __forceinline__ float cdx_act_silu_grad(float x) {
+    const float sg = 1.0f / (1.0f + __expf(-x));
+    return sg * (1.0f + x * (1.0f - sg));
+}
 __device__ __forceinline__ float cdx_act_relu(float x) { return fmaxf(x, 0.f); }
 // 0.5 x (1 + tanh u) == x * sigmoid(2u): one v_exp, one v_rcp, no branches
 __device__ __forceinline__ float cdx_act_gelu_tanh(float x) {

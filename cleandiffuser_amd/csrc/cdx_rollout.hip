@@ -25,12 +25,7 @@
 #include "cdx_act.h"
 #include "cdx_rowtile.h"
 
-extern void cdx_set_err(const char* msg);
-
 namespace {
-
-constexpr int RO_XLD = 64;       // row stride of the (16 x A) state / gradient tiles (A <= 64)
-constexpr int RO_GLD = 68;       // row stride of the head-gradient tile (an MFMA A operand: padded against bank conflicts)
 
 // the step record, plus the two derivatives of the update the backward pass uses:
 //   x' = cx * x + cp * P (+ noise)   with P the CLIPPED prediction (d x'/d x at fixed P, d x'/d P)
@@ -45,7 +40,7 @@ struct RoArgs {
 };
 
 __host__ __device__ inline int ro_ld(int A, int E, int O, int W) {        // row stride of the two activation images
-    const int f16 = (A + E + O + 15) & ~15;
+    const int f16 = ro_r16(A + E + O);
     return (f16 > W ? f16 : W) + 4;
 }
 
@@ -56,7 +51,7 @@ __global__ __launch_bounds__(256) void cdx_rollout_fwd_kernel(const RoArgs a) {
     extern __shared__ __attribute__((aligned(16))) float ro_lds[];
     const cdx_rollout& r = a.r;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int B = r.B, A = r.A, E = r.E, O = r.O, W = r.W, S = r.S, F = A + E + O, F16 = (F + 15) & ~15;
+    const int B = r.B, A = r.A, E = r.E, O = r.O, W = r.W, S = r.S, F = A + E + O, F16 = ro_r16(F);
     const int ld = ro_ld(A, E, O, W);
     const int row0 = blockIdx.x * RO_ROWS;
     float* bufA = ro_lds;                       // [16][ld]
@@ -145,7 +140,7 @@ __global__ __launch_bounds__(256) void cdx_rollout_bwd_kernel(const RoArgs a) {
     float* gxs = bufB + RO_ROWS * ld;           // [16][64] d loss / d x_{s+1}, then d loss / d x_s
     float* gdir = gxs + RO_ROWS * RO_XLD;       // [16][64] the part of d loss / d x_s that does not pass through the network
     float* ghd = gdir + RO_ROWS * RO_XLD;       // [16][68] d loss / d P_raw, zero up to column 64 (an MFMA A operand)
-    float* gcs = ghd + RO_ROWS * RO_GLD;        // [16][O]  d loss / d cond, summed over the steps
+    float* gcs = ghd + RO_ROWS * RO_ALD;        // [16][O]  d loss / d cond, summed over the steps
     const bool want_cond = r.cond != nullptr && r.g_cond != nullptr;
     const size_t SBW = (size_t)S * B * W;
 
@@ -190,12 +185,12 @@ __global__ __launch_bounds__(256) void cdx_rollout_bwd_kernel(const RoArgs a) {
             } else if (e < A) {
                 gdir[i] = 0.f;
             }
-            ghd[rr * RO_GLD + e] = gp;
+            ghd[rr * RO_ALD + e] = gp;
         }
         __syncthreads();
         // head^T, then the three hidden layers^T: G_l = (G_{l+1} W_{l+1}) * Mish'(Z_l), written over Z_l
         const float* src = ghd;
-        int src_ld = RO_GLD, K = A;
+        int src_ld = RO_ALD, K = A;
         float* dst = bufA;
         for (int l = 2; l >= 0; --l) {
             const float* w = l == 2 ? r.wh : l == 1 ? r.w3 : r.w2;         // (K, W) row-major: the layer ABOVE Z_l
@@ -244,26 +239,15 @@ __global__ __launch_bounds__(256) void cdx_rollout_bwd_kernel(const RoArgs a) {
 // host side
 // ------------------------------------------------------------------------------------------------
 int ro_check(const cdx_rollout* r, bool bwd, const char* who) {
-    char msg[160];
-    auto fail = [&](const char* what) {
-        snprintf(msg, sizeof(msg), "%s: %s", who, what);
-        cdx_set_err(msg);
-        return CDX_EINVAL;
-    };
+    auto fail = [&](const char* what) { return ro_fail(who, what); };
     if (!r) return fail("null request");
     if (r->B < 0 || r->A <= 0 || r->E <= 0 || r->O < 0 || r->W <= 0) return fail("bad size");
     if (r->S < 1 || r->S > CDX_ROLLOUT_MAX_STEPS) return fail("S must be 1 .. CDX_ROLLOUT_MAX_STEPS");
-    if (r->W % 16 != 0 || r->W > 512) return fail("W must be a multiple of 16, at most 512");
-    if (r->A + r->E + r->O > 512) return fail("A + E + O must be at most 512");
-    if (r->A > 64) return fail("A must be at most 64");
+    if (r->W % 16 != 0 || r->W > RO_MAX_WIDTH) return fail("W must be a multiple of 16, at most 512");
+    if (r->A + r->E + r->O > RO_MAX_WIDTH) return fail("A + E + O must be at most 512");
+    if (r->A > RO_MAX_X) return fail("A must be at most 64");
     if (!r->steps) return fail("null pointer: steps");
-    for (int i = 0; i < r->S; ++i) {
-        const cdx_step& st = r->steps[i];
-        if (st.kind < 0 || st.kind > 2) return fail("step kind must be 0, 1 or 2");
-        if (st.vsel < 0 || st.vsel > 1) return fail("step vsel must be 0 or 1 (no multistep memory)");
-        if (st.flags != 0) return fail("step flags are not supported");
-        if (st.noise_idx >= 0 && !r->noise) return fail("step draws noise but noise == NULL");
-    }
+    if (const int rs = ro_check_steps(r->steps, r->S, r->noise != nullptr, fail); rs != CDX_OK) return rs;
     if (r->B == 0) return CDX_OK;
     if (!r->w1 || !r->b1 || !r->w2 || !r->b2 || !r->w3 || !r->b3 || !r->wh || !r->bh) return fail("null pointer: weights");
     if (!r->temb || !r->x_in) return fail("null pointer: temb / x_in");
@@ -303,22 +287,10 @@ int ro_launch(const cdx_rollout* r, void* hip_stream, bool bwd) {
     ro_pack(r, &a);
     const int ld = ro_ld(r->A, r->E, r->O, r->W);
     size_t floats = (size_t)2 * RO_ROWS * ld + (size_t)2 * RO_ROWS * RO_XLD;
-    if (bwd) floats += (size_t)RO_ROWS * RO_GLD + (size_t)RO_ROWS * r->O;
+    if (bwd) floats += (size_t)RO_ROWS * RO_ALD + (size_t)RO_ROWS * r->O;
     const size_t lds = floats * sizeof(float);                          // <= 66 KB + 44 KB
     static size_t raised[2] = {0, 0};
-    const void* fn = bwd ? reinterpret_cast<const void*>(cdx_rollout_bwd_kernel) : reinterpret_cast<const void*>(cdx_rollout_fwd_kernel);
-    if (lds > 48 * 1024 && lds > raised[bwd]) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { cdx_set_err(hipGetErrorString(e)); return CDX_EHIP; }
-        raised[bwd] = lds;
-    }
-    const dim3 grid((unsigned)((r->B + RO_ROWS - 1) / RO_ROWS));
-    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-    if (bwd) hipLaunchKernelGGL(cdx_rollout_bwd_kernel, grid, dim3(256), lds, s, a);
-    else hipLaunchKernelGGL(cdx_rollout_fwd_kernel, grid, dim3(256), lds, s, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { cdx_set_err(hipGetErrorString(e)); return CDX_EHIP; }
-    return CDX_OK;
+    return ro_launch_tiles(bwd ? cdx_rollout_bwd_kernel : cdx_rollout_fwd_kernel, a, r->B, lds, hip_stream, raised[bwd]);
 }
 
 }  // namespace

@@ -1,18 +1,26 @@
-// cdx_rowtile.h -- the product routine of the row-tile kernels (cdx_rollout.hip, cdx_energy.hip): one workgroup of 4 wave64 owns 16 rows,
-// activations live in LDS, weights are read from global memory (L2-resident, the same for every workgroup), products run on
-// v_mfma_f32_16x16x4_f32 (exact fp32, rows on the M axis; lane maps: cdx_probe_mfma_layout); and what both need to run the solver step
-// of cdx_step.h on their (16 x A) state tile.
+// cdx_rowtile.h -- what the row-tile kernels share (cdx_rollout.hip, cdx_energy.hip, cdx_cep.hip; cdx_energy_mlp.h builds on it): one
+// workgroup of 4 wave64 owns 16 rows, activations live in LDS, weights are read from global memory (L2-resident, the same for every
+// workgroup), products run on v_mfma_f32_16x16x4_f32 (exact fp32, rows on the M axis; lane maps: cdx_probe_mfma_layout).  Device side: the
+// product routine, the tile strides and loader, and what the sampling kernels need to run the solver step of cdx_step.h on their (16 x A) state
+// tile.  Host side (the end of the file): the size limits, the failure helper, the admission of step records and the one launcher.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "cdx_step.h"
+
+extern void cdx_set_err(const char* msg);
 
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int RO_ROWS = 16;      // rows of a tile = the M side of one 16x16x4 MFMA
+constexpr int RO_XLD = 64;       // row stride of a (16 x A) state / prediction / gradient tile (A <= 64)
+constexpr int RO_ALD = 68;       // row stride of such a tile when it is an MFMA A operand: padded against bank conflicts, zero past A
+
+__host__ __device__ inline int ro_r16(int v) { return (v + 15) & ~15; }
 
 // four consecutive k of one weight column n (zero outside the matrix).  TRANS = false: the weight is (N, K) row-major (nn.Linear.weight
 // in a forward product), TRANS = true: (K, N) row-major (the same tensor in the transposed product of the backward pass: 16 lanes x 4 B
@@ -79,6 +87,18 @@ __device__ __forceinline__ void ro_product(const float* in, int ld, const float*
     }
 }
 
+// rows [row0, row0 + 16) of the row-major (.., C) matrix `src` as an MFMA A operand t [16][ld]: columns [0, fill) are written, zero past
+// C and past row `rows`; src_row(row) is the row of `src` behind row `row` of the batch.  No barrier.
+template <class Row, class SrcRow>
+__device__ __forceinline__ void ro_load_rows(float* t, int ld, int fill, const float* __restrict__ src, int C, Row row0, Row rows, int tid,
+                                             SrcRow src_row) {
+    for (int i = tid; i < RO_ROWS * fill; i += 256) {
+        const int rr = i / fill, c = i - rr * fill;
+        const Row row = row0 + rr;
+        t[rr * ld + c] = (c < C && row < rows) ? src[(size_t)src_row(row) * C + c] : 0.f;
+    }
+}
+
 // what a row-tile kernel carries of a cdx_step in its argument block (the entry points admit kinds 0-2 with vsel <= 1 and no flags:
 // no multistep memory, no push, k[4] unused)
 struct RowStep {
@@ -108,5 +128,46 @@ struct RowStepIO {
     __device__ void push(float) const {}
     __device__ void push_edm(float, float) const {}
 };
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+constexpr int RO_MAX_X = 64, RO_MAX_EMB = 128, RO_MAX_WIDTH = 512, RO_MAX_CONCAT = 1024;   // A; E, Ec; a layer's width, O, A + E + O; in + in2
+
+// "<entry point>: <what>" -> cdx_last_error(), CDX_EINVAL
+inline int ro_fail(const char* who, const char* what) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "%s: %s", who, what);
+    cdx_set_err(msg);
+    return CDX_EINVAL;
+}
+
+// the step records a row-tile kernel takes (RowStep): kinds 0-2 without multistep memory, no flags, noise there when a step draws it
+template <class Fail>
+int ro_check_steps(const cdx_step* steps, int S, bool has_noise, Fail fail) {
+    for (int i = 0; i < S; ++i) {
+        const cdx_step& st = steps[i];
+        if (st.kind < 0 || st.kind > 2) return fail("step kind must be 0, 1 or 2");
+        if (st.vsel < 0 || st.vsel > 1) return fail("step vsel must be 0 or 1 (no multistep memory)");
+        if (st.flags != 0) return fail("step flags are not supported");
+        if (st.noise_idx >= 0 && !has_noise) return fail("step draws noise but noise == NULL");
+    }
+    return CDX_OK;
+}
+
+// one workgroup of 256 threads per 16 rows; `raised` is the kernel's own high-water mark of the attribute that admits > 48 KiB of LDS
+template <class Args>
+int ro_launch_tiles(void (*kernel)(Args), const Args& args, long long rows, size_t lds, void* hip_stream, size_t& raised) {
+    if (lds > 48 * 1024 && lds > raised) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) { cdx_set_err(hipGetErrorString(e)); return CDX_EHIP; }
+        raised = lds;
+    }
+    const dim3 grid((unsigned)((rows + RO_ROWS - 1) / RO_ROWS));
+    hipLaunchKernelGGL(kernel, grid, dim3(256), lds, reinterpret_cast<hipStream_t>(hip_stream), args);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { cdx_set_err(hipGetErrorString(e)); return CDX_EHIP; }
+    return CDX_OK;
+}
 
 }  // namespace

@@ -23,14 +23,14 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from . import blocks, mlp_grad, train
+from . import blocks, train
 from . import runtime as R
+from .energy import MAX_EMB, MAX_HIDDEN, MAX_LDS, MAX_OBS, MAX_WIDTH, MAX_X  # noqa: F401  (the limits of the one energy model)
+from .energy import _silu_grad, classifier_lds, classifier_within_limits, describe_classifier as describe, energy_model
+from .rowtile import ALD, ROWS, declare, on_device
 
-MAX_HIDDEN = 4                                         # CDX_ENERGY_MAX_HIDDEN
-MAX_WIDTH, MAX_X, MAX_EMB, MAX_OBS = 512, 64, 128, 512
-MAX_LDS = 160 * 1024
 GROUPS = (1, 2, 4, 8, 16)                              # K: a 16-row tile holds whole softmax groups
-_ROWS, _ALD, _SC = 16, 68, 64                          # RO_ROWS, CEP_ALD, CEP_SC of the kernel
+_SC = 64                                               # CEP_SC of the kernel
 
 _FP, _I = ctypes.c_void_p, ctypes.c_int32
 
@@ -42,19 +42,9 @@ class CdxCepStep(ctypes.Structure):
                 ("feat", _FP), ("H", _FP), ("G", _FP), ("G_out", _FP), ("G_act", _FP), ("G_obs", _FP), ("stats", _FP)]
 
 
-_declared = False
-
-
 def _lib():
-    global _declared
-    lib = R.load_library()
-    if not _declared:
-        lib.cdx_cep_lds_bytes.argtypes = [ctypes.POINTER(CdxCepStep)]
-        lib.cdx_cep_lds_bytes.restype = ctypes.c_longlong
-        lib.cdx_cep_step_f32.argtypes = [ctypes.POINTER(CdxCepStep), ctypes.c_void_p]
-        lib.cdx_cep_step_f32.restype = ctypes.c_int
-        _declared = True
-    return lib
+    return declare(R.load_library(), {"cdx_cep_lds_bytes": ([ctypes.POINTER(CdxCepStep)], ctypes.c_longlong),
+                                      "cdx_cep_step_f32": ([ctypes.POINTER(CdxCepStep), ctypes.c_void_p], ctypes.c_int)})
 
 
 def enabled() -> bool:
@@ -62,25 +52,8 @@ def enabled() -> bool:
 
 
 # ------------------------------------------------------------------------------------------------------------------- #
-# The net as the kernel reads it                                                                                              #
+# The net as the kernel reads it: ``describe`` = ``energy.describe_classifier``                                               #
 # ------------------------------------------------------------------------------------------------------------------- #
-def describe(net) -> Optional[SimpleNamespace]:
-    """QGPONNClassifier -> its sizes and Linears in the order of the request's weights (obs_proj, act_proj, the hidden layers, the head),
-    or None unless the mlp is SiLU hidden layers and an identity output to one scalar."""
-    layers = mlp_grad._mlp_layers(net.mlp)
-    if layers is None or len(layers) < 2 or any(act != "silu" for _, act in layers[:-1]) or layers[-1][1] != "none":
-        return None
-    lins = [net.obs_proj, net.act_proj] + [lin for lin, _ in layers]
-    if any(type(m) is not nn.Linear or m.bias is None for m in lins):
-        return None
-    ec = net.act_proj.out_features
-    hidden, last = lins[2:-1], lins[-1]
-    widths = [ec * 3] + [lin.out_features for lin in hidden]
-    if net.obs_proj.out_features != ec or last.out_features != 1 or [lin.in_features for lin in hidden + [last]] != widths:
-        return None
-    return SimpleNamespace(Ec=ec, O=net.obs_proj.in_features, A=net.act_proj.in_features, hidden=widths[1:], lins=lins)
-
-
 def weights_of(desc):
     """[obs_w, obs_b, act_w, act_b, w_0, b_0, ..., w_o, b_o]: the parameters themselves."""
     return [p for lin in desc.lins for p in (lin.weight, lin.bias)]
@@ -88,15 +61,13 @@ def weights_of(desc):
 
 def lds_bytes(desc) -> int:
     """The kernel's LDS plan (cep_plan of csrc/cdx_cep.hip; ``cdx_cep_lds_bytes``)."""
-    r16 = lambda v: (v + 15) & ~15                                                       # noqa: E731
-    maxw = max([r16(desc.O), r16(3 * desc.Ec)] + list(desc.hidden))
-    return 4 * (2 * _ROWS * (maxw + 4) + sum(_ROWS * w for w in desc.hidden) + _ROWS * _ALD + _SC)
+    maxw, pre = classifier_lds(desc)
+    return 4 * (2 * ROWS * (maxw + 4) + pre + ROWS * ALD + _SC)
 
 
 def within_limits(desc, k: int) -> bool:
     """The limits ``cdx_cep_step_f32`` refuses with CDX_EINVAL."""
-    return (k in GROUPS and 1 <= len(desc.hidden) <= MAX_HIDDEN and all(w % 16 == 0 and 0 < w <= MAX_WIDTH for w in desc.hidden)
-            and 0 < desc.A <= MAX_X and 0 < desc.Ec <= MAX_EMB and 0 < desc.O <= MAX_OBS and lds_bytes(desc) <= MAX_LDS)
+    return k in GROUPS and classifier_within_limits(desc, desc.A) and lds_bytes(desc) <= MAX_LDS
 
 
 # ------------------------------------------------------------------------------------------------------------------- #
@@ -153,11 +124,6 @@ def scalars(sums, b: int, k: int):
 # ------------------------------------------------------------------------------------------------------------------- #
 # The same step in plain torch (any dtype, any device)                                                                        #
 # ------------------------------------------------------------------------------------------------------------------- #
-def _silu_grad(z):
-    sg = torch.sigmoid(z)
-    return sg * (1. + z * (1. - sg))
-
-
 def reference_step(q) -> SimpleNamespace:
     """What ``cdx_cep_step_f32`` computes, into the same buffers (explicit backward formulas, no autograd) -> the four scalars and the
     gradient of every parameter (the products the device path hands to ``cdx_conv_wgrad_batch_f32``), in the order of ``weights_of``."""
@@ -165,17 +131,14 @@ def reference_step(q) -> SimpleNamespace:
     b, k = q.B, q.K
     rep = lambda t: t.repeat_interleave(k, 0)                                             # noqa: E731   (row r = state r // K)
     q.feat.copy_(torch.cat([rep(q.obs @ w[0].t() + w[1]), q.x @ w[2].t() + w[3], rep(q.temb)], -1))
-    h, pres = q.feat, []
-    for l in range(len(q.hidden)):
-        pres.append(h @ w[4 + 2 * l].t() + w[5 + 2 * l])
-        q.H[l].copy_(nn.functional.silu(pres[-1]))
-        h = q.H[l]
-    t = torch.tanh((h @ w[-2].t() + w[-1]) / 10)[:, 0]
-    f, y = (10 * t).view(b, k), q.soft.view(b, k)
+    f, dt, pres = energy_model(q.feat, w[4:-2:2], w[5:-2:2], w[-2], w[-1])
+    for l, pre in enumerate(pres):
+        q.H[l].copy_(nn.functional.silu(pre))
+    f, y = f.view(b, k), q.soft.view(b, k)
     lse = torch.logsumexp(f, 1, keepdim=True)
     q.stats.copy_(torch.stack([-(y * (f - lse)).sum(1), f.max(1)[0], f.min(1)[0], f.sum(1)], 1))
     g_f = (torch.softmax(f, 1) * y.sum(1, keepdim=True) - y) / b
-    q.G_out.copy_(g_f.reshape(-1) * (1. - t * t))
+    q.G_out.copy_(g_f.reshape(-1) * dt[:, 0])
     g = q.G_out[:, None] * w[-2] * _silu_grad(pres[-1])
     for l in range(len(q.hidden) - 1, -1, -1):
         q.G[l].copy_(g)
@@ -241,8 +204,6 @@ def try_cep_update(clf, x, t, y, update_ema: bool = True) -> Optional[dict]:
         return None
     if not _fused_optimiser(clf.optim):
         return None
-    on_device = lambda v, shape: (torch.is_tensor(v) and v.is_cuda and v.dtype == torch.float32                      # noqa: E731
-                                  and tuple(v.shape) == shape)
     if not isinstance(y, dict) or not on_device(y.get("soft_label"), (b, k, 1)) or not on_device(y.get("obs"), (b, desc.O)):
         return None
     if not (torch.is_tensor(t) and t.is_cuda and tuple(t.shape) == (b,)):

@@ -12,6 +12,7 @@ made before the launch on the library's GEMM: ``den_c`` = ``t_layer(map_noise(t_
 the C call and what the GPU tests compare the traces against.  ``CDX_ENERGY=0`` keeps the host loop.
 """
 import ctypes
+import functools
 import os
 import weakref
 from types import SimpleNamespace
@@ -23,13 +24,11 @@ import torch.nn as nn
 
 from . import blocks, mlp_grad
 from . import runtime as R
-from .plan import KIND_DDIM, KIND_DDPM, KIND_LINEAR
-from .rollout import _noise_index, reference_step
+from .rowtile import ALD, ROWS, XLD, declare, noise_index, on_device, r16, reference_step, solver_env, step_admissible
 
 MAX_STEPS, MAX_BLOCKS, MAX_HIDDEN = 64, 8, 4          # CDX_ENERGY_MAX_*
 MAX_WIDTH, MAX_CONCAT, MAX_X, MAX_EMB, MAX_OBS = 512, 1024, 64, 128, 512
 MAX_LDS = 160 * 1024
-_ROWS, _XLD, _ALD = 16, 64, 68                        # RO_ROWS, EN_XLD, EN_ALD of the kernel
 
 _FP, _I = ctypes.c_void_p, ctypes.c_int32
 
@@ -50,19 +49,9 @@ class CdxEnergyGuided(ctypes.Structure):
                 ("x_out", _FP), ("logp_out", _FP), ("trace_pred", _FP), ("trace_grad", _FP), ("trace_logp", _FP)]
 
 
-_declared = False
-
-
 def _lib():
-    global _declared
-    lib = R.load_library()
-    if not _declared:
-        lib.cdx_energy_guided_lds_bytes.argtypes = [ctypes.POINTER(CdxEnergyGuided)]
-        lib.cdx_energy_guided_lds_bytes.restype = ctypes.c_longlong
-        lib.cdx_energy_guided_run.argtypes = [ctypes.POINTER(CdxEnergyGuided), ctypes.c_void_p]
-        lib.cdx_energy_guided_run.restype = ctypes.c_int
-        _declared = True
-    return lib
+    return declare(R.load_library(), {"cdx_energy_guided_lds_bytes": ([ctypes.POINTER(CdxEnergyGuided)], ctypes.c_longlong),
+                                      "cdx_energy_guided_run": ([ctypes.POINTER(CdxEnergyGuided), ctypes.c_void_p], ctypes.c_int)})
 
 
 def enabled() -> bool:
@@ -106,24 +95,39 @@ def describe_denoiser(net) -> Optional[SimpleNamespace]:
                            A=net.out_layer.out_features, E=emb)
 
 
-def describe_classifier(net) -> Optional[SimpleNamespace]:
-    """QGPONNClassifier -> its weights and the transposed operands of the explicit backward (made here, once per weight version: see
-    ``_bound``), or None unless the mlp is SiLU hidden layers and an identity output to one scalar."""
+class _Classifier(SimpleNamespace):
+    """What ``describe_classifier`` returns.  The transposed operands of the guided kernel's backward are copies, made when first read
+    (the guided route keeps the description per weight version, see ``_bound``; the training step never reads them): `wt[0]` = the
+    act_proj columns [Ec, 2 Ec) of w[0] transposed (Ec, hidden[0]), `wt[l]` = w[l] transposed, `act_wt`."""
+
+    @functools.cached_property
+    def wt(self):
+        return [self.w[0][:, self.Ec:2 * self.Ec].t().contiguous()] + [m.t().contiguous() for m in self.w[1:]]
+
+    @functools.cached_property
+    def act_wt(self):
+        return self.act_w.t().contiguous()
+
+
+def describe_classifier(net) -> Optional[_Classifier]:
+    """QGPONNClassifier -> its sizes, its Linears in the order of the training request's weights (`lins`: obs_proj, act_proj, the hidden
+    layers, the head) and their detached parameters as the guided request names them, or None unless the mlp is SiLU hidden layers and an
+    identity output to one scalar, every layer a plain nn.Linear with a bias whose input is the width before it."""
     layers = mlp_grad._mlp_layers(net.mlp)
     if layers is None or len(layers) < 2 or any(act != "silu" for _, act in layers[:-1]) or layers[-1][1] != "none":
         return None
-    if any(type(m) is not nn.Linear or m.bias is None for m in (net.obs_proj, net.act_proj)) or any(lin.bias is None for lin, _ in layers):
+    lins = [net.obs_proj, net.act_proj] + [lin for lin, _ in layers]
+    if any(type(m) is not nn.Linear or m.bias is None for m in lins):
         return None
     ec = net.act_proj.out_features
-    hidden, last = [lin for lin, _ in layers[:-1]], layers[-1][0]
-    if net.obs_proj.out_features != ec or hidden[0].in_features != 3 * ec or last.out_features != 1:
+    hidden, last = lins[2:-1], lins[-1]
+    widths = [ec * 3] + [lin.out_features for lin in hidden]
+    if net.obs_proj.out_features != ec or last.out_features != 1 or [lin.in_features for lin in hidden + [last]] != widths:
         return None
-    w = [lin.weight.detach() for lin in hidden]
-    wt = [w[0][:, ec:2 * ec].t().contiguous()] + [m.t().contiguous() for m in w[1:]]
-    return SimpleNamespace(Ec=ec, O=net.obs_proj.in_features, hidden=[lin.out_features for lin in hidden], w=w,
-                           b=[lin.bias.detach() for lin in hidden], wt=wt, wo=last.weight.detach(), bo=last.bias.detach(),
-                           obs_w=net.obs_proj.weight.detach(), obs_b=net.obs_proj.bias.detach(), act_w=net.act_proj.weight.detach(),
-                           act_b=net.act_proj.bias.detach(), act_wt=net.act_proj.weight.detach().t().contiguous())
+    return _Classifier(Ec=ec, O=net.obs_proj.in_features, A=net.act_proj.in_features, hidden=widths[1:], lins=lins,
+                       w=[lin.weight.detach() for lin in hidden], b=[lin.bias.detach() for lin in hidden], wo=last.weight.detach(),
+                       bo=last.bias.detach(), obs_w=net.obs_proj.weight.detach(), obs_b=net.obs_proj.bias.detach(),
+                       act_w=net.act_proj.weight.detach(), act_b=net.act_proj.bias.detach())
 
 
 def _tensors(desc):
@@ -149,23 +153,32 @@ def _bound(net, make):
     return hit[1]
 
 
+def classifier_lds(clf):
+    """(the widest MFMA operand, the floats of the saved pre-activations) of the energy model: em_plan of csrc/cdx_energy_mlp.h."""
+    return max([r16(clf.O), r16(3 * clf.Ec)] + list(clf.hidden)), sum(ROWS * w for w in clf.hidden)
+
+
+def classifier_within_limits(clf, a: int) -> bool:
+    """The sizes of the energy model em_plan refuses, for states of width `a`."""
+    return (1 <= len(clf.hidden) <= MAX_HIDDEN and all(w % 16 == 0 and 0 < w <= MAX_WIDTH for w in clf.hidden)
+            and 0 < a <= MAX_X and 0 < clf.Ec <= MAX_EMB and 0 < clf.O <= MAX_OBS)
+
+
 def lds_bytes(den, clf) -> int:
     """The kernel's LDS plan (en_plan of csrc/cdx_energy.hip; ``cdx_energy_guided_lds_bytes``)."""
-    r16 = lambda v: (v + 15) & ~15                                                       # noqa: E731
-    maxw = max([r16(clf.O), r16(3 * clf.Ec)] + clf.hidden + [r.out for r in den.rows])
-    img = _ROWS * (maxw + 4)
+    clf_w, pre = classifier_lds(clf)
+    img = ROWS * (max([clf_w] + [r.out for r in den.rows]) + 4)
     pops = sum(r.in2 > 0 for r in den.rows)
-    stack = sum(_ROWS * (r.out + 4) for r in den.rows[den.n_down - pops:den.n_down])
-    region = max(3 * img + stack, 2 * img + sum(_ROWS * w for w in clf.hidden))
-    return 4 * (region + _ROWS * (r16(den.E) + 4) + _ROWS * _ALD + 2 * _ROWS * _XLD + _ROWS * r16(clf.Ec) + 2 * _ROWS)
+    stack = sum(ROWS * (r.out + 4) for r in den.rows[den.n_down - pops:den.n_down])
+    region = max(3 * img + stack, 2 * img + pre)
+    return 4 * (region + ROWS * (r16(den.E) + 4) + ROWS * ALD + 2 * ROWS * XLD + ROWS * r16(clf.Ec) + 2 * ROWS)
 
 
 def within_limits(den, clf, n_steps: int) -> bool:
     """The limits ``cdx_energy_guided_run`` refuses with CDX_EINVAL."""
-    widths = [r.out for r in den.rows] + clf.hidden
-    return (all(w % 16 == 0 and w <= MAX_WIDTH for w in widths) and all(r.in_ + r.in2 <= MAX_CONCAT for r in den.rows)
-            and den.A <= MAX_X and den.E <= MAX_EMB and clf.Ec <= MAX_EMB and clf.O <= MAX_OBS and 1 <= n_steps <= MAX_STEPS
-            and len(den.rows) <= MAX_BLOCKS and 1 <= len(clf.hidden) <= MAX_HIDDEN and lds_bytes(den, clf) <= MAX_LDS)
+    return (classifier_within_limits(clf, den.A) and all(r.out % 16 == 0 and r.out <= MAX_WIDTH for r in den.rows)
+            and all(r.in_ + r.in2 <= MAX_CONCAT for r in den.rows) and den.E <= MAX_EMB and 1 <= n_steps <= MAX_STEPS
+            and len(den.rows) <= MAX_BLOCKS and lds_bytes(den, clf) <= MAX_LDS)
 
 
 # ------------------------------------------------------------------------------------------------------------------- #
@@ -196,12 +209,7 @@ def _c_request(q):
         dst.in_, dst.in2, dst.out = r.in_, r.in2, r.out
         for name in ("w1", "b1", "w2", "b2", "wc", "bc", "ws", "bs"):
             setattr(dst, name, p(getattr(r, name)))
-    steps = (R.CdxStep * len(q.steps))()
-    for i, (st, ni) in enumerate(zip(q.steps, _noise_index(q.steps))):
-        steps[i].kind, steps[i].vsel, steps[i].noise_idx, steps[i].push, steps[i].flags = st.kind, st.vsel, ni, 0, int(st.flags)
-        steps[i].alpha, steps[i].sigma = st.alpha, st.sigma
-        for j in range(5):
-            steps[i].k[j] = st.k[j]
+    steps = R.pack_steps(q.steps)
     cg = (ctypes.c_float * len(q.cg_scale))(*[float(np.float32(v)) for v in q.cg_scale])
     c = CdxEnergyGuided(B=q.B, A=q.A, E=q.E, O=q.O, S=q.S, Ec=q.Ec, n_blocks=len(den.rows), n_down=den.n_down, n_hidden=len(clf.hidden),
                         predict_noise=int(q.predict_noise), clip=int(q.clip), blocks=rows, out_w=p(den.out_w), out_b=p(den.out_b),
@@ -230,6 +238,17 @@ def _silu_grad(z):
     return sg * (1. + z * (1. - sg))
 
 
+def energy_model(feat, ws, bs, wo, bo):
+    """The mlp of QGPONNClassifier on the feature rows [obs_proj(obs) | act_proj(x) | temb] -> (f = 10 tanh(o / 10) (R,),
+    1 - tanh^2(o / 10) (R, 1), the hidden pre-activations): the one torch restatement of csrc/cdx_energy_mlp.h's forward."""
+    h, pres = feat, []
+    for w, b in zip(ws, bs):
+        pres.append(h @ w.t() + b)
+        h = nn.functional.silu(pres[-1])
+    t = torch.tanh((h @ wo.t() + bo) / 10)
+    return (10 * t)[:, 0], 1. - t * t, pres
+
+
 def _denoiser(den, x, c):
     """``SfBCUNet.forward`` on the block table: the raw prediction."""
     h, kept = x, []
@@ -243,25 +262,18 @@ def _denoiser(den, x, c):
     return h @ den.out_w.t() + den.out_b
 
 
-def _energy(clf, obs_feat, x, temb):
-    """(logp (B,), d logp / d f (B, 1), the hidden pre-activations) of the energy model at x with the time-embedding row `temb`."""
-    h = torch.cat([obs_feat, x @ clf.act_w.t() + clf.act_b, temb.expand(x.shape[0], clf.Ec)], -1)
-    pres = []
-    for w, b in zip(clf.w, clf.b):
-        pres.append(h @ w.t() + b)
-        h = nn.functional.silu(pres[-1])
-    t = torch.tanh((h @ clf.wo.t() + clf.bo) / 10)
-    return (10 * t)[:, 0], 1. - t * t, pres
-
-
 def reference_run(q) -> None:
     """What ``cdx_energy_guided_run`` computes, step by step, into the same outputs and traces."""
     den, clf = q.den, q.clf
     x = q.x_in
     obs_feat = q.obs @ clf.obs_w.t() + clf.obs_b
-    for s, (st, ni) in enumerate(zip(q.steps, _noise_index(q.steps))):
+
+    def energy_at(x, temb):                                            # (logp (B,), d logp / d f (B, 1), the hidden pre-activations)
+        feat = torch.cat([obs_feat, x @ clf.act_w.t() + clf.act_b, temb.expand(x.shape[0], clf.Ec)], -1)
+        return energy_model(feat, clf.w, clf.b, clf.wo, clf.bo)
+    for s, (st, ni) in enumerate(zip(q.steps, noise_index(q.steps))):
         pred = _denoiser(den, x, q.den_c[s] if q.cond is None else q.den_c[s] + q.cond)
-        logp, g, pres = _energy(clf, obs_feat, x, q.clf_temb[s])
+        logp, g, pres = energy_at(x, q.clf_temb[s])
         g = g * clf.wo * _silu_grad(pres[-1])                          # explicit backward: x SiLU'(pre), transposed weights
         for l in range(len(pres) - 1, 0, -1):
             g = (g @ clf.wt[l].t()) * _silu_grad(pres[l - 1])
@@ -271,7 +283,7 @@ def reference_run(q) -> None:
         x = reference_step(q, st, ni, x, pred + q.cg_scale[s] * g)
     q.x_out.copy_(x)
     if q.logp_out is not None:
-        q.logp_out.copy_(_energy(clf, obs_feat, x, q.clf_temb[q.S])[0][:, None])
+        q.logp_out.copy_(energy_at(x, q.clf_temb[q.S])[0][:, None])
 
 
 # ------------------------------------------------------------------------------------------------------------------- #
@@ -320,39 +332,28 @@ def try_energy_guided(solver, model, plan, xt, prior, cond_vec, w_cfg, condition
         return None
     clf_net = clf.model_ema
     b, a = xt.shape
-    on_device = lambda t, shape: (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32                      # noqa: E731
-                                  and tuple(t.shape) == shape)
-    if w_cfg not in (0.0, 1.0):
-        return None
     steps = plan.steps
-    if any(st.kind not in (KIND_DDPM, KIND_DDIM, KIND_LINEAR) or st.vsel > 1 or st.flags for st in steps):
-        return None                                       # (the ...2M solvers carry x_theta from step to step, EDM plans: host loop)
+    if w_cfg not in (0.0, 1.0) or not step_admissible(steps, MAX_STEPS):
+        return None
     den, cl = _bound(net, lambda: describe_denoiser(net)), _bound(clf_net, lambda: describe_classifier(clf_net))
-    if den is None or cl is None or den.A != a or clf_net.act_proj.in_features != a or not within_limits(den, cl, len(steps)):
+    if den is None or cl is None or den.A != a or cl.A != a or not within_limits(den, cl, len(steps)):
         return None
     if not on_device(condition_cg, (b, cl.O)) or (w_cfg == 1.0 and not on_device(cond_vec, (b, den.E))):
         return None
     if not all(t.is_contiguous() and t.dtype == torch.float32 for t in _tensors(den) + _tensors(cl)):
         return None
     dev = xt.device
-    try:
-        fix_mask = R._dense_hd(solver.fix_mask, 1, a, dev)
-        clip = bool(getattr(plan, "clip_each_step", True)) and solver.clip_pred
-        x_min = R._dense_hd(getattr(solver, "x_min", None), 1, a, dev) if clip else None
-        x_max = R._dense_hd(getattr(solver, "x_max", None), 1, a, dev) if clip else None
-    except (ValueError, RuntimeError):
+    env = solver_env(solver, plan, prior, b, a, dev)
+    if env is None:
         return None
-    if fix_mask is not None and (not torch.is_tensor(prior) or tuple(prior.shape) != (b, a)):
-        return None
+    prior, fix_mask, x_min, x_max, clip = env
     with torch.no_grad():
         den_c, clf_temb = step_tables(net, clf_net, plan, dev)
         pn = R._predicts_noise(plan, solver)
         noise = feed.many(xt, plan.n_noise)
-        flat = lambda t: None if t is None else t.detach().reshape(-1).contiguous()      # noqa: E731
         q = make_request(den, cl, den_c, clf_temb, R._f32c(cond_vec.detach(), dev) if w_cfg == 1.0 else None,
                          R._f32c(condition_cg.detach(), dev), steps, guidance_scale(plan, w_cg, pn), pn, clip, R._f32c(xt.detach(), dev),
-                         R._f32c(prior.detach(), dev) if fix_mask is not None else None, flat(fix_mask), flat(x_min), flat(x_max),
-                         None if noise is None else R._f32c(noise.detach(), dev))
+                         prior, fix_mask, x_min, x_max, None if noise is None else R._f32c(noise.detach(), dev))
         globals()["native_run"](q)                           # (looked up per call: the CPU tests patch it)
     out = q.x_out
     out._cdx_logp = q.logp_out

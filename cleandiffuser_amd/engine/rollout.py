@@ -27,7 +27,8 @@ from torch.autograd.function import once_differentiable
 
 from . import blocks, train
 from . import runtime as R
-from .plan import KIND_DDIM, KIND_DDPM, KIND_LINEAR, V_XTHETA
+from .plan import KIND_DDIM, KIND_DDPM, V_XTHETA
+from .rowtile import _bounds, declare, noise_index, reference_step, solver_env, step_admissible  # noqa: F401  (_bounds: tests/rollout_cases.py)
 
 MAX_STEPS = 64             # CDX_ROLLOUT_MAX_STEPS: the step records travel in the kernel argument
 MAX_WIDTH, MAX_FEATURES, MAX_X = 512, 512, 64
@@ -46,18 +47,9 @@ class CdxRollout(ctypes.Structure):
                 ("g_temb", ctypes.c_void_p)]
 
 
-_declared = False
-
-
 def _lib():
-    global _declared
-    lib = R.load_library()
-    if not _declared:
-        for f in (lib.cdx_rollout_fwd_f32, lib.cdx_rollout_bwd_f32):
-            f.argtypes = [ctypes.POINTER(CdxRollout), ctypes.c_void_p]
-            f.restype = ctypes.c_int
-        _declared = True
-    return lib
+    proto = ([ctypes.POINTER(CdxRollout), ctypes.c_void_p], ctypes.c_int)
+    return declare(R.load_library(), {"cdx_rollout_fwd_f32": proto, "cdx_rollout_bwd_f32": proto})
 
 
 def enabled() -> bool:
@@ -84,21 +76,8 @@ def make_request(weights, temb, cond, x_in, prior, fix_mask, x_min, x_max, noise
         g_out=None, G_head=None, g_x=None, g_cond=None, g_temb=None)
 
 
-def _noise_index(steps):
-    idx, k = [], 0
-    for st in steps:
-        idx.append(k if st.noise else -1)
-        k += 1 if st.noise else 0
-    return idx
-
-
 def _c_request(q) -> "tuple":
-    steps = (R.CdxStep * len(q.steps))()
-    for i, (st, ni) in enumerate(zip(q.steps, _noise_index(q.steps))):
-        steps[i].kind, steps[i].vsel, steps[i].noise_idx, steps[i].push, steps[i].flags = st.kind, st.vsel, ni, 0, int(st.flags)
-        steps[i].alpha, steps[i].sigma = st.alpha, st.sigma
-        for j in range(5):
-            steps[i].k[j] = st.k[j]
+    steps = R.pack_steps(q.steps)
     p = blocks._p
     w = q.weights
     c = CdxRollout(B=q.B, A=q.A, E=q.E, O=q.O, W=q.W, S=q.S, predict_noise=int(q.predict_noise), clip=int(q.clip),
@@ -148,52 +127,12 @@ def _step_derivatives(st, predict_noise: bool):
     return ax + ae * ex + at * tx, ae * ep + at * tp
 
 
-def _bounds(q, st, x):
-    """(lower, upper) of the clamp at this step, each a tensor or None (``BaseDiffusionSDE.clip_prediction``)."""
-    if not q.clip:
-        return None, None
-    if q.predict_noise:
-        lo = (x - st.alpha * q.x_max) / st.sigma if q.x_max is not None else None
-        hi = (x - st.alpha * q.x_min) / st.sigma if q.x_min is not None else None
-        return lo, hi
-    return q.x_min, q.x_max
-
-
-def reference_step(q, st, ni: int, x, p):
-    """x_{s+1} from x_s and the raw prediction `p`: clip, eps <-> x0, the affine update of the record, `+ k z` (draw `ni` of q.noise),
-    fix-mask blend -- the solver step of the row-tile kernels (csrc/cdx_rollout.hip, csrc/cdx_energy.hip)."""
-    lo, hi = _bounds(q, st, x)
-    if lo is not None:
-        p = torch.maximum(p, lo)
-    if hi is not None:
-        p = torch.minimum(p, hi)
-    k0, k1, k2, k3, _ = st.k
-    if q.predict_noise:
-        eps, xth = p, (x - st.sigma * p) / st.alpha
-    else:
-        eps, xth = (x - st.alpha * p) / st.sigma, p
-    if st.kind == KIND_DDPM:
-        new = k0 * (x - k1 * eps) + k2 * eps
-        if ni >= 0:
-            new = new + k3 * q.noise[ni]
-    elif st.kind == KIND_DDIM:
-        new = k0 * ((x - k1 * eps) / k2) + k3 * eps
-    else:
-        assert st.kind == KIND_LINEAR and st.vsel <= 1
-        new = k0 * x - k1 * (xth if st.vsel == V_XTHETA else eps)
-        if ni >= 0:
-            new = new + k2 * q.noise[ni]
-    if q.fix_mask is not None:
-        new = new * (1. - q.fix_mask) + q.prior * q.fix_mask
-    return new
-
-
 def reference_forward(q) -> None:
     """What ``cdx_rollout_fwd_f32`` computes, step by step, into the same buffers."""
     w1, b1, w2, b2, w3, b3, wh, bh = q.weights
     x = q.x_in
     q.X[0] = x
-    for s, (st, ni) in enumerate(zip(q.steps, _noise_index(q.steps))):
+    for s, (st, ni) in enumerate(zip(q.steps, noise_index(q.steps))):
         cond = q.cond if q.cond is not None else x.new_zeros(q.B, q.O)
         feat = torch.cat([x, q.temb[s].expand(q.B, q.E), cond], -1)
         q.feat[s] = feat
@@ -358,9 +297,7 @@ def try_rollout(solver, model, plan, xt, prior, cond_vec, w_cfg, w_cg, feed) -> 
     if not (w_cg == 0.0 or getattr(solver, "classifier", None) is None):
         return None
     steps = plan.steps
-    if not 1 <= len(steps) <= MAX_STEPS or any(st.kind not in (KIND_DDPM, KIND_DDIM, KIND_LINEAR) or st.vsel > 1 or st.flags for st in steps):
-        return None                                       # (the ...2M solvers carry x_theta from step to step: host loop)
-    if getattr(prior, "requires_grad", False):
+    if not step_admissible(steps, MAX_STEPS) or getattr(prior, "requires_grad", False):
         return None
     trunk = _trunk(net)
     b, a = xt.shape
@@ -372,21 +309,11 @@ def try_rollout(solver, model, plan, xt, prior, cond_vec, w_cfg, w_cg, feed) -> 
     if e <= 0 or o < 0 or (cond is not None and (cond.dtype != torch.float32 or not cond.is_cuda or tuple(cond.shape) != (b, o))):
         return None
     dev = xt.device
-    try:
-        fix_mask = R._dense_hd(solver.fix_mask, 1, a, dev)
-        clip = bool(getattr(plan, "clip_each_step", True)) and solver.clip_pred
-        x_min = R._dense_hd(getattr(solver, "x_min", None), 1, a, dev) if clip else None
-        x_max = R._dense_hd(getattr(solver, "x_max", None), 1, a, dev) if clip else None
-    except (ValueError, RuntimeError):
-        return None
-    if any(t is not None and t.requires_grad for t in (fix_mask, x_min, x_max)):
-        return None
-    if fix_mask is not None and (not torch.is_tensor(prior) or tuple(prior.shape) != (b, a)):
+    env = solver_env(solver, plan, prior, b, a, dev, refuse_grad=True)
+    if env is None:
         return None
     temb = time_table(net, plan, dev)
     noise = feed.many(xt, plan.n_noise)
-    flat = lambda t: None if t is None else t.detach().reshape(-1).contiguous()      # noqa: E731
-    env = (R._f32c(prior.detach(), dev) if fix_mask is not None else None, flat(fix_mask), flat(x_min), flat(x_max), steps,
-           R._predicts_noise(plan, solver), clip)
+    env = (*env[:4], steps, R._predicts_noise(plan, solver), env[4])
     return _Rollout.apply(xt, cond, temb, None if noise is None else R._f32c(noise.detach(), dev),
                           l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias, head.weight, head.bias, env)

@@ -307,11 +307,12 @@ def device_times(plan, device) -> torch.Tensor:
 
 
 def pack_steps(plan):
-    """plan.Step list -> cdx_step array on the host; noise_idx numbers the stochastic steps.  At least one record long: callers
-    hand its address to C also for an empty plan."""
-    arr = (CdxStep * max(len(plan.steps), 1))()
+    """A plan (or its list of plan.Step) -> cdx_step array on the host; noise_idx numbers the stochastic steps.  At least one record
+    long: callers hand its address to C also for an empty plan."""
+    steps = getattr(plan, "steps", plan)
+    arr = (CdxStep * max(len(steps), 1))()
     k = 0
-    for i, st in enumerate(plan.steps):
+    for i, st in enumerate(steps):
         arr[i].kind, arr[i].vsel, arr[i].push, arr[i].flags = st.kind, st.vsel, int(st.push), int(st.flags)
         arr[i].alpha, arr[i].sigma = st.alpha, st.sigma
         for j in range(5):
