@@ -1,6 +1,6 @@
-// cdx_act.h -- the per-element activation formulas of the library, one device function per CDX_ACT_* id (include/cdx.h) plus the Mish
-// and SiLU derivatives.  gm_act (cdx_gemm.hip), act2_f (cdx_unet2.hip), the rollout kernels (cdx_rollout.hip) and the energy model of
-// the row-tile kernels (cdx_energy_mlp.h, cdx_energy.hip) dispatch to these.  Two use sites write their formula out instead (Mish in gm_act, GELU_ERF in act2_f): the same arithmetic, but through the call hipcc emits other
+// cdx_act.h -- the per-element activation formulas of the library, one device function per CDX_ACT_* id (include/cdx.h) plus the Mish,
+// SiLU, ReLU and tanh derivatives.  gm_act (cdx_gemm.hip), act2_f (cdx_unet2.hip), the rollout kernels (cdx_rollout.hip), the energy model
+// of the row-tile kernels (cdx_energy_mlp.h, cdx_energy.hip) and the critic towers (cdx_tower.hip) dispatch to these.  Two use sites write their formula out instead (Mish in gm_act, GELU_ERF in act2_f): the same arithmetic, but through the call hipcc emits other
 // code for the kernels around them.  A change to a formula here goes to those two as well.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -38,6 +38,7 @@ __device__ __forceinline__ float cdx_act_silu_grad(float x) {
     return sg * (1.0f + x * (1.0f - sg));
 }
 __device__ __forceinline__ float cdx_act_relu(float x) { return fmaxf(x, 0.f); }
+__device__ __forceinline__ float cdx_act_relu_grad(float x) { return x > 0.f ? 1.0f : 0.f; }      // (0 at 0, as ATen's threshold_backward)
 // 0.5 x (1 + tanh u) == x * sigmoid(2u): one v_exp, one v_rcp, no branches
 __device__ __forceinline__ float cdx_act_gelu_tanh(float x) {
     const float u2 = 1.5957691216057308f * (x + 0.044715f * x * x * x);
@@ -47,4 +48,10 @@ __device__ __forceinline__ float cdx_act_gelu_tanh(float x) {
 __device__ __forceinline__ float cdx_act_tanh(float x) {
     const float t = __expf(-2.0f * fabsf(x));
     return copysignf((1.0f - t) * __builtin_amdgcn_rcpf(1.0f + t), x);
+}
+// d/dx tanh(x) = 1 - tanh^2(x) = 4 t / (1 + t)^2, t = e^{-2|x|}: no cancellation where tanh saturates
+__device__ __forceinline__ float cdx_act_tanh_grad(float x) {
+    const float t = __expf(-2.0f * fabsf(x));
+    const float d = 1.0f + t;
+    return 4.0f * t / (d * d);
 }

@@ -1,4 +1,4 @@
-// cdx_rowtile.h -- what the row-tile kernels share (cdx_rollout.hip, cdx_energy.hip, cdx_cep.hip; cdx_energy_mlp.h builds on it): one
+// cdx_rowtile.h -- what the row-tile kernels share (cdx_rollout.hip, cdx_energy.hip, cdx_cep.hip, cdx_tower.hip; cdx_energy_mlp.h builds on it): one
 // workgroup of 4 wave64 owns 16 rows, activations live in LDS, weights are read from global memory (L2-resident, the same for every
 // workgroup), products run on v_mfma_f32_16x16x4_f32 (exact fp32, rows on the M axis; lane maps: cdx_probe_mfma_layout).  Device side: the
 // product routine, the tile strides and loader, and what the sampling kernels need to run the solver step of cdx_step.h on their (16 x A) state
@@ -155,15 +155,17 @@ int ro_check_steps(const cdx_step* steps, int S, bool has_noise, Fail fail) {
     return CDX_OK;
 }
 
-// one workgroup of 256 threads per 16 rows; `raised` is the kernel's own high-water mark of the attribute that admits > 48 KiB of LDS
+// one workgroup of 256 threads per 16 rows (times `grid_y`: the twin towers of cdx_tower.hip); `raised` is the kernel's own high-water
+// mark of the attribute that admits > 48 KiB of LDS
 template <class Args>
-int ro_launch_tiles(void (*kernel)(Args), const Args& args, long long rows, size_t lds, void* hip_stream, size_t& raised) {
+int ro_launch_tiles(void (*kernel)(Args), const Args& args, long long rows, size_t lds, void* hip_stream, size_t& raised,
+                    unsigned grid_y = 1) {
     if (lds > 48 * 1024 && lds > raised) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) { cdx_set_err(hipGetErrorString(e)); return CDX_EHIP; }
         raised = lds;
     }
-    const dim3 grid((unsigned)((rows + RO_ROWS - 1) / RO_ROWS));
+    const dim3 grid((unsigned)((rows + RO_ROWS - 1) / RO_ROWS), grid_y);
     hipLaunchKernelGGL(kernel, grid, dim3(256), lds, reinterpret_cast<hipStream_t>(hip_stream), args);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { cdx_set_err(hipGetErrorString(e)); return CDX_EHIP; }

@@ -1,0 +1,351 @@
+// cdx_tower.hip -- the critics' Linear -> [LayerNorm] -> activation towers, forward and backward-data, for one 16-row tile per workgroup.
+//
+// DQLCritic, TwinQ and V (utils/critics.py; reference utils/building_blocks.py:111-147, utils/iql.py:7-37) are stepped on every gradient
+// update of the dql / edp / idql / qgpo pipelines.  As library nodes a tower costs one launch per Linear, LayerNorm and activation forward
+// and about twice that backward: a TwinQ.both with its backward is about 40 launches of a few microseconds of work each.  Rows are
+// independent, so one workgroup of 4 wave64 owns 16 rows of one tower (grid (ceil(R / 16), n_towers): twin towers read the same rows) and
+// runs, with the product routine of the row-tile kernels (cdx_rowtile.h: activations in LDS, weights from global memory,
+// v_mfma_f32_16x16x4_f32),
+//   forward   per layer z = h W^T + b (ro_product<false>); with a norm, 16 lanes per row take the mean and then the biased variance of the
+//             centred values over the row in LDS (two passes, a fixed butterfly), xhat = (z - mean) rstd, y = xhat gamma + beta; h = act(y);
+//   backward  per layer from the top: y from the saved P_l (xhat or z), dy = dH act'(y), with a norm g = dy gamma,
+//             dz = rstd (g - mean(g) - xhat mean(g xhat)) and the tile's column sums of dy and dy xhat (rows in order), then
+//             dH_{l-1} = dz W_l on the live weight (ro_product<true>); at layer 0 that is g_x.
+// H_l, P_l, rstd_l (forward) and G_l = dz, Sb, Sg (backward) go to global memory: the weight and bias sums over the rows are the caller's
+// (one cdx_conv_wgrad_batch_f32), the gain and shift sums over the tiles one cdx_colsum_batch_f32 (below).  Rows of the last tile past R
+// carry a zero gradient and nothing is written for them.  No atomics in the two tower kernels, every element is produced by one fixed
+// lane in one fixed order: bit-reproducible.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include "../../include/cdx.h"
+#include "cdx_act.h"
+#include "cdx_rowtile.h"
+
+namespace {
+
+constexpr long long TW_LDS_MAX = 160 * 1024;
+
+// the LDS plan, in floats: two activation images [16][ld]
+struct TowerPlan {
+    int32_t ld;                                   // row stride of the images: the widest operand (up to the next multiple of 16) + 4
+    int32_t off_col[CDX_TOWER_MAX_LAYERS];        // the widths before layer l: its (R, width[l]) matrix starts at float R * off_col[l]
+    int32_t total;
+};
+
+struct TowerArgs {
+    cdx_tower g;
+    TowerPlan p;
+};
+static_assert(sizeof(TowerArgs) <= 4096, "the kernel argument segment holds 4 KiB");
+
+__device__ __forceinline__ float tw_act(int act, float y) {
+    switch (act) {
+        case CDX_ACT_MISH: return cdx_act_mish(y);
+        case CDX_ACT_SILU: return cdx_act_silu(y);
+        case CDX_ACT_RELU: return cdx_act_relu(y);
+        case CDX_ACT_TANH: return cdx_act_tanh(y);
+        default: return y;
+    }
+}
+__device__ __forceinline__ float tw_act_grad(int act, float y) {
+    switch (act) {
+        case CDX_ACT_MISH: return cdx_act_mish_grad(y);
+        case CDX_ACT_SILU: return cdx_act_silu_grad(y);
+        case CDX_ACT_RELU: return cdx_act_relu_grad(y);
+        case CDX_ACT_TANH: return cdx_act_tanh_grad(y);
+        default: return 1.0f;
+    }
+}
+// the sum over the 16 lanes of a row (tid >> 4): a butterfly, the same bits in every lane
+__device__ __forceinline__ float tw_sum16(float v) {
+    v += __shfl_xor(v, 8, 16);
+    v += __shfl_xor(v, 4, 16);
+    v += __shfl_xor(v, 2, 16);
+    v += __shfl_xor(v, 1, 16);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void cdx_tower_fwd_kernel(const TowerArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float tw_lds[];
+    const cdx_tower& g = a.g;
+    const TowerPlan& p = a.p;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int t = blockIdx.y, L = g.n_layers, ld = p.ld;
+    const long long R = g.R, row0 = (long long)blockIdx.x * RO_ROWS;
+    const int rr = tid >> 4, sub = tid & 15;          // the norm's view: 16 lanes per row
+    const bool live = row0 + rr < R;
+    auto image = [&](int i) { return tw_lds + (size_t)i * RO_ROWS * ld; };
+
+    ro_load_rows(image(0), ld, ro_r16(g.K0), g.x, g.K0, row0, R, tid, [](long long row) { return row; });
+    __syncthreads();
+    int src = 0;
+    for (int l = 0; l < L; ++l) {
+        const int W = g.width[l], K = l ? g.width[l - 1] : g.K0, act = g.act[l];
+        const float* bias = g.b[t][l];
+        float* dst = image(src ^ 1);
+        float* Hl = l == L - 1 ? g.out[t] : (g.save ? g.H[t] + (size_t)R * p.off_col[l] : nullptr);
+        float* Pl = g.save ? g.P[t] + (size_t)R * p.off_col[l] : nullptr;
+        if (!g.norm[l]) {
+            ro_product<false>(image(src), ld, g.w[t][l], K, W, K, lane, wave, [&](int r, int n, float v) {
+                const float z = v + bias[n];
+                const float h = tw_act(act, z);
+                dst[r * ld + n] = h;
+                if (row0 + r < R) {
+                    const size_t at = (size_t)(row0 + r) * W + n;
+                    if (Hl) Hl[at] = h;
+                    if (Pl) Pl[at] = z;
+                }
+            });
+            __syncthreads();
+        } else {
+            ro_product<false>(image(src), ld, g.w[t][l], K, W, K, lane, wave, [&](int r, int n, float v) { dst[r * ld + n] = v + bias[n]; });
+            __syncthreads();
+            const float* gamma = g.gamma[t][l];
+            const float* beta = g.beta[t][l];
+            float* zr = dst + rr * ld;
+            float s = 0.f;
+            for (int c = sub; c < W; c += 16) s += zr[c];
+            const float mean = tw_sum16(s) / (float)W;
+            float q = 0.f;
+            for (int c = sub; c < W; c += 16) {
+                const float d = zr[c] - mean;
+                q += d * d;
+            }
+            const float rstd = 1.0f / sqrtf(tw_sum16(q) / (float)W + g.eps[l]);
+            for (int c = sub; c < W; c += 16) {
+                const float xhat = (zr[c] - mean) * rstd;
+                const float h = tw_act(act, xhat * gamma[c] + beta[c]);
+                zr[c] = h;
+                if (live) {
+                    const size_t at = (size_t)(row0 + rr) * W + c;
+                    if (Hl) Hl[at] = h;
+                    if (Pl) Pl[at] = xhat;
+                }
+            }
+            if (sub == 0 && live && g.save) g.rstd[t][(size_t)l * R + (row0 + rr)] = rstd;
+            __syncthreads();
+        }
+        src ^= 1;
+    }
+}
+
+__global__ __launch_bounds__(256) void cdx_tower_bwd_kernel(const TowerArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float tw_lds[];
+    const cdx_tower& g = a.g;
+    const TowerPlan& p = a.p;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int t = blockIdx.y, L = g.n_layers, ld = p.ld;
+    const long long R = g.R, row0 = (long long)blockIdx.x * RO_ROWS, tiles = gridDim.x;
+    const int rr = tid >> 4, sub = tid & 15;
+    const long long row = row0 + rr;
+    const bool live = row < R;
+    auto image = [&](int i) { return tw_lds + (size_t)i * RO_ROWS * ld; };
+
+    const int WL = g.width[L - 1];
+    ro_load_rows(image(0), ld, ro_r16(WL), g.g_out[t], WL, row0, R, tid, [](long long r) { return r; });
+    __syncthreads();
+    int cur = 0;
+    for (int l = L - 1; l >= 0; --l) {
+        const int W = g.width[l], K = l ? g.width[l - 1] : g.K0, act = g.act[l];
+        float* d = image(cur);                        // dH_l, then dy, then dz: the A operand of the transposed product
+        float* o = image(cur ^ 1);                    // xhat of a normed layer, then dH_{l-1}
+        const float* Pl = g.P[t] + (size_t)R * p.off_col[l];
+        float* Gl = g.want_params ? g.G[t] + (size_t)R * p.off_col[l] : nullptr;
+        float* dr = d + rr * ld;
+        if (!g.norm[l]) {
+            for (int c = sub; c < W; c += 16) {
+                const float z = live ? Pl[(size_t)row * W + c] : 0.f;
+                const float dz = dr[c] * tw_act_grad(act, z);
+                dr[c] = dz;
+                if (Gl && live) Gl[(size_t)row * W + c] = dz;
+            }
+            __syncthreads();
+        } else {
+            const float* gamma = g.gamma[t][l];
+            const float* beta = g.beta[t][l];
+            float* xr = o + rr * ld;
+            const float rs = live ? g.rstd[t][(size_t)l * R + row] : 0.f;
+            float s1 = 0.f, s2 = 0.f;
+            for (int c = sub; c < W; c += 16) {
+                const float xh = live ? Pl[(size_t)row * W + c] : 0.f;
+                const float dy = dr[c] * tw_act_grad(act, xh * gamma[c] + beta[c]);
+                const float gg = dy * gamma[c];
+                s1 += gg;
+                s2 += gg * xh;
+                dr[c] = dy;
+                xr[c] = xh;
+            }
+            s1 = tw_sum16(s1) / (float)W;
+            s2 = tw_sum16(s2) / (float)W;
+            __syncthreads();
+            if (g.want_params) {                      // the tile's share of the shift / gain gradients: its 16 rows in order
+                float* Sb = g.Sb[t] + (size_t)tiles * p.off_col[l] + (size_t)blockIdx.x * W;
+                float* Sg = g.Sg[t] + (size_t)tiles * p.off_col[l] + (size_t)blockIdx.x * W;
+                for (int c = tid; c < W; c += 256) {
+                    float sb = 0.f, sg = 0.f;
+                    for (int r = 0; r < RO_ROWS; ++r) {
+                        const float dy = d[r * ld + c];
+                        sb += dy;
+                        sg += dy * o[r * ld + c];
+                    }
+                    Sb[c] = sb;
+                    Sg[c] = sg;
+                }
+            }
+            __syncthreads();
+            for (int c = sub; c < W; c += 16) {
+                const float dz = rs * (dr[c] * gamma[c] - s1 - xr[c] * s2);
+                dr[c] = dz;
+                if (Gl && live) Gl[(size_t)row * W + c] = dz;
+            }
+            __syncthreads();
+        }
+        if (l == 0) {
+            if (g.want_gx) {
+                float* gx = g.g_x[t];
+                ro_product<true>(d, ld, g.w[t][0], K, K, W, lane, wave, [&](int r, int n, float v) {
+                    if (row0 + r < R) gx[(size_t)(row0 + r) * K + n] = v;
+                });
+            }
+        } else {
+            ro_product<true>(d, ld, g.w[t][l], K, K, W, lane, wave, [&](int r, int n, float v) { o[r * ld + n] = v; });
+            __syncthreads();
+            cur ^= 1;
+        }
+    }
+}
+
+// out[c] += sum_r src[r][c] for every job: 64 columns x 64 rows per workgroup, the body of cdx_colsum_f32 (cdx_train.hip)
+constexpr int CSB_ROWS = 64;
+__global__ __launch_bounds__(256) void cdx_colsum_batch_kernel(const cdx_colsum_batch B) {
+    __shared__ float part[4][64];
+    int j = 0;
+    while (j + 1 < B.n_jobs && (int)blockIdx.x >= B.wg_start[j + 1]) ++j;
+    const cdx_colsum_job q = B.job[j];
+    const int local = (int)blockIdx.x - B.wg_start[j];
+    const int col_tiles = (q.cols + 63) / 64;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int c = (local % col_tiles) * 64 + tx;
+    const long long r0 = (long long)(local / col_tiles) * CSB_ROWS;
+    const long long r1 = r0 + CSB_ROWS < q.rows ? r0 + CSB_ROWS : q.rows;
+    float s = 0.f;
+    if (c < q.cols)
+        for (long long r = r0 + ty; r < r1; r += 4) s += q.src[r * q.ld + c];
+    part[ty][tx] = s;
+    __syncthreads();
+    if (ty == 0 && c < q.cols) atomicAdd(q.out + c, (part[0][tx] + part[1][tx]) + (part[2][tx] + part[3][tx]));
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+// sizes and the LDS plan: everything that can be checked without touching device memory
+int tower_plan(const char* who, const cdx_tower* g, TowerPlan* p) {
+    auto fail = [&](const char* what) { return ro_fail(who, what); };
+    if (!g) return fail("null request");
+    if (g->R < 0 || g->R > 0x7fffffff - RO_ROWS) return fail("bad size: R");
+    if (g->n_towers != 1 && g->n_towers != 2) return fail("n_towers must be 1 or 2");
+    if (g->n_layers < 1 || g->n_layers > CDX_TOWER_MAX_LAYERS) return fail("n_layers must be 1 .. CDX_TOWER_MAX_LAYERS");
+    if (g->K0 <= 0 || g->K0 > RO_MAX_WIDTH) return fail("K0 must be 1 .. 512");
+    int maxw = ro_r16(g->K0), cols = 0;
+    for (int l = 0; l < CDX_TOWER_MAX_LAYERS; ++l) p->off_col[l] = 0;
+    for (int l = 0; l < g->n_layers; ++l) {
+        const int w = g->width[l];
+        if (l == g->n_layers - 1) {
+            if (w <= 0 || w > RO_MAX_X) return fail("the last width must be 1 .. 64");
+        } else if (w <= 0 || w % 16 != 0 || w > RO_MAX_WIDTH) {
+            return fail("every width but the last must be a multiple of 16, at most 512");
+        }
+        const int a = g->act[l];
+        if (a != CDX_ACT_NONE && a != CDX_ACT_MISH && a != CDX_ACT_SILU && a != CDX_ACT_RELU && a != CDX_ACT_TANH)
+            return fail("activation must be none, mish, silu, relu or tanh");
+        if (g->norm[l] && !(g->eps[l] > 0.f)) return fail("eps must be positive");
+        maxw = ro_r16(w) > maxw ? ro_r16(w) : maxw;
+        p->off_col[l] = cols;
+        cols += w;
+    }
+    p->ld = maxw + 4;
+    p->total = 2 * RO_ROWS * p->ld;
+    return CDX_OK;
+}
+
+int tower_check(const char* who, const cdx_tower* g, TowerPlan* p, bool backward) {
+    auto fail = [&](const char* what) { return ro_fail(who, what); };
+    const int rc = tower_plan(who, g, p);
+    if (rc != CDX_OK) return rc;
+    if ((long long)p->total * (long long)sizeof(float) > TW_LDS_MAX) return fail("the LDS plan exceeds 160 KiB");
+    if (g->R == 0) return CDX_OK;
+    if (!g->x && !backward) return fail("null pointer: x");
+    const bool saved = backward || g->save;
+    for (int t = 0; t < g->n_towers; ++t) {
+        for (int l = 0; l < g->n_layers; ++l) {
+            if (!g->w[t][l] || (!backward && !g->b[t][l])) return fail("null pointer: weights");
+            if (g->norm[l] && (!g->gamma[t][l] || !g->beta[t][l])) return fail("null pointer: norm parameters");
+        }
+        if (!backward && !g->out[t]) return fail("null pointer: out");
+        if (saved && (!g->P[t] || !g->rstd[t])) return fail("null pointer: P / rstd");
+        if (!backward && g->save && g->n_layers > 1 && !g->H[t]) return fail("null pointer: H");
+        if (backward) {
+            if (!g->g_out[t]) return fail("null pointer: g_out");
+            if (g->want_params && (!g->G[t] || !g->Sb[t] || !g->Sg[t])) return fail("null pointer: G / Sb / Sg");
+            if (g->want_gx && !g->g_x[t]) return fail("null pointer: g_x");
+        }
+    }
+    return CDX_OK;
+}
+
+int tower_launch(const char* who, void (*kernel)(TowerArgs), const cdx_tower* g, void* hip_stream, bool backward, size_t& raised) {
+    cdx_set_err("");
+    TowerArgs a;
+    const int rc = tower_check(who, g, &a.p, backward);
+    if (rc != CDX_OK || g->R == 0) return rc;
+    a.g = *g;
+    return ro_launch_tiles(kernel, a, g->R, (size_t)a.p.total * sizeof(float), hip_stream, raised, (unsigned)g->n_towers);
+}
+
+}  // namespace
+
+extern "C" {
+
+long long cdx_tower_lds_bytes(const cdx_tower* g) {
+    cdx_set_err("");
+    TowerPlan p;
+    const int rc = tower_plan("cdx_tower_lds_bytes", g, &p);
+    return rc != CDX_OK ? rc : (long long)p.total * (long long)sizeof(float);
+}
+
+int cdx_tower_fwd_f32(const cdx_tower* g, void* hip_stream) {
+    static size_t raised = 0;
+    return tower_launch("cdx_tower_fwd_f32", cdx_tower_fwd_kernel, g, hip_stream, false, raised);
+}
+
+int cdx_tower_bwd_f32(const cdx_tower* g, void* hip_stream) {
+    static size_t raised = 0;
+    return tower_launch("cdx_tower_bwd_f32", cdx_tower_bwd_kernel, g, hip_stream, true, raised);
+}
+
+int cdx_colsum_batch_f32(const cdx_colsum_batch* B, void* hip_stream) {
+    cdx_set_err("");
+    auto fail = [](const char* what) { return ro_fail("cdx_colsum_batch_f32", what); };
+    if (!B) return fail("null request");
+    if (B->n_jobs < 0 || B->n_jobs > CDX_COLSUM_BATCH) return fail("n_jobs must be 0 .. CDX_COLSUM_BATCH");
+    if (B->n_jobs == 0) return CDX_OK;
+    if (B->wg_start[0] != 0) return fail("wg_start[0] must be 0");
+    for (int j = 0; j < B->n_jobs; ++j) {
+        const cdx_colsum_job& q = B->job[j];
+        if (q.rows < 0 || q.cols <= 0 || q.ld < q.cols) return fail("bad shape");
+        if (q.rows > 0 && (!q.src || !q.out)) return fail("null pointer");
+        const long long wgs = (long long)((q.cols + 63) / 64) * ((q.rows + CSB_ROWS - 1) / CSB_ROWS);
+        if ((long long)B->wg_start[j + 1] - B->wg_start[j] != wgs) return fail("wg_start does not match the jobs");
+    }
+    const int grid = B->wg_start[B->n_jobs];
+    if (grid == 0) return CDX_OK;
+    hipLaunchKernelGGL(cdx_colsum_batch_kernel, dim3((unsigned)grid), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream), *B);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { cdx_set_err(hipGetErrorString(e)); return CDX_EHIP; }
+    return CDX_OK;
+}
+
+}  // extern "C"

@@ -5,9 +5,11 @@ attribute names, hence the same ``state_dict`` keys).  Diffusion Veteran's horiz
 
 Execution: every head here is a chain of ``Linear -> [LayerNorm] -> activation`` over rows, so on a ROCm device without
 autograd the chain runs through ``engine/heads.py`` (fp32-MFMA GEMM with fused bias/activation epilogue + one fused
-LayerNorm/activation launch per layer); with autograd ON (the critics' training steps) through ``engine/train.py:chain_forward`` --
-the same library nodes the denoisers train on, forward and backward --, IQL's two Adam optimisers and its Polyak target update on
-``cdx_optim_f32``; on CPU the stock modules run.
+LayerNorm/activation launch per layer); with autograd ON (the critics' training steps) a whole tower, or the twin towers of a critic
+together, is one forward and one backward row-tile launch (``engine/tower.py``: ``DQLCritic`` by default, ``TwinQ`` / ``V`` with
+``CDX_TOWER=1`` -- the measurement of DESIGN.md 3m; ``CDX_TOWER=0`` or a tower it does not take: ``engine/train.py:chain_forward``, the
+library nodes the denoisers train on), IQL's two Adam optimisers and its Polyak target update on ``cdx_optim_f32``; on CPU the stock
+modules run.
 """
 from copy import deepcopy
 
@@ -16,12 +18,22 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 
-def _rows(seq: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
-    from ..engine import heads, train
+def _rows(seq: nn.Sequential, x: torch.Tensor, fused: bool = False) -> torch.Tensor:
+    from ..engine import heads, tower, train
+    y = tower.try_tower((seq,), x, fused)      # the whole tower on one forward and one backward launch (engine/tower.py)
+    if y is not None:
+        return y[0]
     if train.supports_chain(seq, x):           # autograd on, ROCm device (the critics' own training steps): library nodes forward and backward
         return train.chain_forward(seq, x)
     y = heads.try_sequential(seq, x)
     return seq(x) if y is None else y
+
+
+def _twin(seq1: nn.Sequential, seq2: nn.Sequential, x: torch.Tensor, fused: bool = False):
+    """(seq1(x), seq2(x)): twin towers over the same rows share their two launches.  `fused`: without being asked (CDX_TOWER=1)?"""
+    from ..engine import tower
+    y = tower.try_tower((seq1, seq2), x, fused)
+    return y if y is not None else (_rows(seq1, x, fused), _rows(seq2, x, fused))
 
 
 class SoftLowerBound(nn.Module):
@@ -62,11 +74,10 @@ class DQLCritic(nn.Module):
         self.q2_model = _q_tower(obs_dim + act_dim, hidden_dim, nn.Tanh(), 3)
 
     def forward(self, obs, act):
-        x = torch.cat([obs, act], dim=-1)
-        return _rows(self.q1_model, x), _rows(self.q2_model, x)
+        return _twin(self.q1_model, self.q2_model, torch.cat([obs, act], dim=-1), fused=True)
 
     def q1(self, obs, act):
-        return _rows(self.q1_model, torch.cat([obs, act], dim=-1))
+        return _rows(self.q1_model, torch.cat([obs, act], dim=-1), fused=True)
 
     def q_min(self, obs, act):
         return torch.min(*self.forward(obs, act))
@@ -79,8 +90,7 @@ class TwinQ(nn.Module):
         self.Q2 = _q_tower(obs_dim + act_dim, hidden_dim, nn.Mish(), 2)
 
     def both(self, obs, act):
-        x = torch.cat([obs, act], -1)
-        return _rows(self.Q1, x), _rows(self.Q2, x)
+        return _twin(self.Q1, self.Q2, torch.cat([obs, act], -1))
 
     def forward(self, obs, act):
         return torch.min(*self.both(obs, act))

@@ -893,6 +893,75 @@ long long cdx_cep_lds_bytes(const cdx_cep_step* g);
 int cdx_cep_step_f32(const cdx_cep_step* g, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The critics' Linear -> [LayerNorm] -> activation towers in ONE forward and ONE backward launch (csrc/cdx_tower.hip).  Purely
+ * additive entries: no existing struct or call changes, so CDX_ABI_VERSION stays 18.  Reference: utils/building_blocks.py:111-147
+ * (DQLCritic), utils/iql.py:7-37 (TwinQ, V): stepped on every gradient update by the dql / edp / idql / qgpo pipelines.
+ * A tower has n_layers layers, layer l = Linear(K_l -> width[l]) with bias, an affine LayerNorm(width[l], eps[l]) when norm[l], then
+ * act[l] in {CDX_ACT_NONE, _MISH, _SILU, _RELU, _TANH}; K_0 = K0, K_l = width[l-1].  n_towers (1 or 2) towers of the same shape read
+ * the same input rows x (R, K0).  One workgroup of 4 wave64 owns 16 rows of one tower: grid (ceil(R / 16), n_towers).
+ *   forward   z = h W^T + b; with a norm: mean and biased variance of the centred values in two passes over the row (as ATen),
+ *             rstd = 1 / sqrt(var + eps), xhat = (z - mean) rstd, y = xhat gamma + beta, otherwise y = z; h = act(y).
+ *             save != 0 writes, per tower, LAYER-major -- layer l's (R, width[l]) row-major matrix starts at float
+ *             R * (width[0] + .. + width[l-1]) -- H_l = h for l < n_layers - 1 and P_l = xhat (normed layer) or z, and rstd_l (R) at float
+ *             R * l; the last layer's h goes to out (R, width[n_layers-1]) either way.  save == 0 writes out only.
+ *   backward  from g_out (R, width[n_layers-1]) top-down: y from P_l, dy = dH act'(y); with a norm g = dy gamma,
+ *             dz = rstd (g - mean(g) - xhat mean(g xhat)) (the formula of cdx_layernorm_bwd_f32), otherwise dz = dy; dH_{l-1} = dz W_l on
+ *             the live weight.  want_params != 0 writes G_l = dz (layer-major as P) and, for normed layers, the sums of dy (Sb) and of
+ *             dy xhat (Sg) over the 16 rows of the tile: layer l's (ceil(R / 16), width[l]) matrix starts at float
+ *             ceil(R / 16) * (width[0] + .. + width[l-1]).  want_gx != 0 writes g_x (R, K0) per tower (the caller adds the two).
+ * The weight / bias gradients are the caller's: one cdx_conv_wgrad_batch_f32 with jobs (G_l, H_{l-1} or x, R); the gain / shift
+ * gradients one cdx_colsum_batch_f32 over Sg / Sb.  Caller-owned memory, one kernel per call enqueued on `hip_stream`, no
+ * synchronisation, no allocation, capturable; no atomics, one fixed lane and order per element: bit-reproducible.
+ * Limits (CDX_EINVAL with a message, before anything is launched): 1 <= n_layers <= CDX_TOWER_MAX_LAYERS; n_towers 1 or 2; K0 <= 512;
+ * every width but the last a multiple of 16 and <= 512; the last <= 64; the LDS plan (cdx_tower_lds_bytes) at most 160 KiB.  R == 0
+ * is CDX_OK.
+ * ---------------------------------------------------------------------------------------------- */
+#define CDX_TOWER_MAX_LAYERS 6
+typedef struct cdx_tower {
+    int32_t R, K0, n_towers, n_layers;
+    int32_t width[CDX_TOWER_MAX_LAYERS];
+    int32_t norm[CDX_TOWER_MAX_LAYERS];                 /* 1: an affine LayerNorm follows the Linear */
+    int32_t act[CDX_TOWER_MAX_LAYERS];                  /* CDX_ACT_NONE / MISH / SILU / RELU / TANH */
+    float eps[CDX_TOWER_MAX_LAYERS];
+    int32_t save;                                       /* forward: write H, P, rstd */
+    int32_t want_gx, want_params;                       /* backward: write g_x; write G, Sb, Sg */
+    const float* x;                                     /* (R, K0) */
+    const float* w[2][CDX_TOWER_MAX_LAYERS];            /* tower t, layer l: (width[l], K_l): nn.Linear.weight as it lives */
+    const float* b[2][CDX_TOWER_MAX_LAYERS];            /* (width[l]) */
+    const float* gamma[2][CDX_TOWER_MAX_LAYERS];        /* (width[l]), normed layers */
+    const float* beta[2][CDX_TOWER_MAX_LAYERS];
+    float* out[2];                                      /* (R, width[n_layers-1]) */
+    float* H[2];                                        /* layer-major, layers 0 .. n_layers - 2 */
+    float* P[2];                                        /* layer-major, every layer */
+    float* rstd[2];                                     /* (n_layers, R) */
+    const float* g_out[2];                              /* (R, width[n_layers-1]) */
+    float* G[2];                                        /* layer-major, every layer */
+    float* Sb[2];                                       /* tile-major partial sums (see above) */
+    float* Sg[2];
+    float* g_x[2];                                      /* (R, K0) */
+} cdx_tower;
+/* bytes of LDS one workgroup of this request needs, or a negative CDX_E* code when the sizes are out of range */
+long long cdx_tower_lds_bytes(const cdx_tower* g);
+int cdx_tower_fwd_f32(const cdx_tower* g, void* hip_stream);
+int cdx_tower_bwd_f32(const cdx_tower* g, void* hip_stream);
+/* up to CDX_COLSUM_BATCH column sums in ONE launch: out[c] += sum_r src[r][c] per job, as cdx_colsum_f32 (`out` zeroed or carrying a
+ * gradient; 64-row slices are combined with float atomics; the job table travels as the kernel argument).  A job with rows == 0 adds
+ * nothing. */
+#define CDX_COLSUM_BATCH 32
+typedef struct cdx_colsum_job {
+    const float* src;
+    float* out;
+    long long rows;
+    int32_t cols, ld;
+} cdx_colsum_job;
+typedef struct cdx_colsum_batch {
+    int32_t n_jobs;
+    int32_t wg_start[CDX_COLSUM_BATCH + 1];             /* first workgroup of job j: it owns ceil(cols / 64) * ceil(rows / 64) of them */
+    cdx_colsum_job job[CDX_COLSUM_BATCH];
+} cdx_colsum_batch;
+int cdx_colsum_batch_f32(const cdx_colsum_batch* batch, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimiser side of DiffusionModel.update(): multi-tensor AdamW + EMA + gradient-norm clipping.
  * Replaces, per update() call, torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW.step() + optimizer.zero_grad() +
  * DiffusionModel.ema_update() (reference diffusion/diffusionsde.py:114-141, diffusion/basic.py:66,83-86): one device table of
