@@ -77,7 +77,7 @@ __global__ __launch_bounds__(OPT_THREADS) void cdx_optim_kernel(cdx_optim_args a
         return;
     }
     if (MODE == CDX_OPT_EMA) {
-        const float r = a.ema_rate, q = 1.f - a.ema_rate;
+        const float r = a.ema_rate, q = a.one_minus_ema_rate;
         for (int i = threadIdx.x; i < len; i += OPT_THREADS) e[i] = e[i] * r + q * p[i];
         return;
     }
@@ -86,8 +86,10 @@ __global__ __launch_bounds__(OPT_THREADS) void cdx_optim_kernel(cdx_optim_args a
     const float clip = (a.max_norm > 0.f) ? a.norm[1] : 1.f;
     const float decay = MODE == CDX_OPT_ADAM ? 1.f : 1.f - a.lr * a.weight_decay;
     const float l2 = MODE == CDX_OPT_ADAM ? a.weight_decay : 0.f;
-    const float w1 = 1.f - a.beta1, w2 = 1.f - a.beta2;
-    const float r = a.ema_rate, q = 1.f - a.ema_rate;
+    // (the complements come from the host, rounded from float64 as torch rounds lerp_'s weight and addcmul_'s value: 1.f - a.beta2 starts
+    //  from the rounded beta2 and is off by up to ulp(beta2) / 2 (1 - beta2) -- 1.3e-5 of exp_avg_sq at beta2 = 0.999)
+    const float w1 = a.one_minus_beta1, w2 = a.one_minus_beta2;
+    const float r = a.ema_rate, q = a.one_minus_ema_rate;
     const bool vec = (((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
                         reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(e)) & 15) == 0);
     auto one = [&](float pp, float gg, float& mm, float& vv) -> float {
@@ -146,7 +148,9 @@ __global__ __launch_bounds__(OPT_THREADS) void cdx_optim_norm_kernel(const float
         const float total = sqrtf(red[0]);
         norm[0] = total;
         const float coef = max_norm / (total + 1e-6f);       // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max = 1)
-        norm[1] = (max_norm > 0.f && coef < 1.f) ? coef : 1.f;
+        // (written so that a NaN norm -- a NaN gradient -- keeps its NaN coefficient, as torch's clamp does: the step then poisons
+        //  every parameter, as the reference's update() does, instead of running unclipped; an infinite norm gives 0)
+        norm[1] = (max_norm > 0.f) ? (coef > 1.f ? 1.f : coef) : 1.f;
     }
 }
 
@@ -174,6 +178,10 @@ extern "C" int cdx_optim_f32(const cdx_optim_args* a, void* hip_stream) {
         }
         if (!(a->bc2_sqrt > 0.f) || !(a->beta1 >= 0.f && a->beta1 < 1.f) || !(a->beta2 >= 0.f && a->beta2 < 1.f)) {
             cdx_set_error("cdx_optim_f32: betas must lie in [0, 1) and bc2_sqrt must be positive");
+            return CDX_EINVAL;
+        }
+        if (!(a->one_minus_beta1 > 0.f && a->one_minus_beta1 <= 1.f) || !(a->one_minus_beta2 > 0.f && a->one_minus_beta2 <= 1.f)) {
+            cdx_set_error("cdx_optim_f32: one_minus_beta1 / one_minus_beta2 (the host's 1 - beta, ABI 19) must lie in (0, 1]");
             return CDX_EINVAL;
         }
         if (a->mode == CDX_OPT_ADAM) hipLaunchKernelGGL(cdx_optim_kernel<CDX_OPT_ADAM>, grid, block, 0, st, *a);

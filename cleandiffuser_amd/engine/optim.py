@@ -34,7 +34,8 @@ class CdxOptimArgs(ctypes.Structure):
                 ("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
                 ("weight_decay", ctypes.c_float), ("step_size", ctypes.c_float), ("bc2_sqrt", ctypes.c_float),
                 ("ema_rate", ctypes.c_float), ("max_norm", ctypes.c_float), ("zero_grad", ctypes.c_int32),
-                ("partial", ctypes.c_void_p), ("norm", ctypes.c_void_p)]
+                ("partial", ctypes.c_void_p), ("norm", ctypes.c_void_p),
+                ("one_minus_beta1", ctypes.c_float), ("one_minus_beta2", ctypes.c_float), ("one_minus_ema_rate", ctypes.c_float)]
 
 
 _declared = False
@@ -109,7 +110,7 @@ def ema_update_native(model: torch.nn.Module, model_ema: torch.nn.Module, rate: 
     cache = model_ema.__dict__.setdefault("_cdx_optim_tables", {})
     tab = _table(cache, "ema", [ps, es], dev)
     _call(CdxOptimArgs(p=tab.row(0), ema=tab.row(1), numel=tab.numel_ptr, chunks=tab.chunks.data_ptr(), n_tensors=tab.n_tensors,
-                       n_chunks=tab.n_chunks, chunk_elems=CHUNK, mode=OPT_EMA, ema_rate=float(rate)), dev)
+                       n_chunks=tab.n_chunks, chunk_elems=CHUNK, mode=OPT_EMA, ema_rate=float(rate), one_minus_ema_rate=1.0 - float(rate)), dev)
     _bump_versions(model_ema.parameters())
     return True
 
@@ -277,7 +278,10 @@ class _FusedStep:
                                    chunk_elems=CHUNK, mode=self._mode_of(group), lr=float(group["lr"]), beta1=float(b1), beta2=float(b2),
                                    eps=float(group["eps"]), weight_decay=float(group["weight_decay"]),
                                    step_size=float(group["lr"]) / (1.0 - b1 ** t), bc2_sqrt=math.sqrt(1.0 - b2 ** t),
-                                   ema_rate=float(rate), max_norm=clip, zero_grad=int(zero_grad), norm=self._norm.data_ptr()), dev)
+                                   ema_rate=float(rate), max_norm=clip, zero_grad=int(zero_grad), norm=self._norm.data_ptr(),
+                                   # (the complements from their float64 values, as torch rounds lerp_'s weight, addcmul_'s value and
+                                   #  add_'s alpha: 1.f - beta2 on the device would start from the ROUNDED beta2)
+                                   one_minus_beta1=1.0 - float(b1), one_minus_beta2=1.0 - float(b2), one_minus_ema_rate=1.0 - float(rate)), dev)
                 _bump_versions(ps)
                 if ema_of is not None:
                     _bump_versions([ema_of[id(p)] for p in ps])
@@ -293,7 +297,8 @@ class _FusedStep:
                     raise RuntimeError("FusedAdamW: `ema` holds parameters outside the fp32 device path")
                 tab = _table(self._tables, "ema_rest", [[p for p, _ in rest], [e for _, e in rest]], dev)
                 _call(CdxOptimArgs(p=tab.row(0), ema=tab.row(1), numel=tab.numel_ptr, chunks=tab.chunks.data_ptr(), n_tensors=tab.n_tensors,
-                                   n_chunks=tab.n_chunks, chunk_elems=CHUNK, mode=OPT_EMA, ema_rate=float(rate)), dev)
+                                   n_chunks=tab.n_chunks, chunk_elems=CHUNK, mode=OPT_EMA, ema_rate=float(rate),
+                                   one_minus_ema_rate=1.0 - float(rate)), dev)
                 _bump_versions([e for _, e in rest])
         return loss
 

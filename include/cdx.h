@@ -18,7 +18,7 @@
 extern "C" {
 #endif
 
-#define CDX_ABI_VERSION 18
+#define CDX_ABI_VERSION 19
 
 #define CDX_OK 0
 #define CDX_EINVAL (-1)   /* bad argument (null pointer, size out of range, misaligned offset) */
@@ -966,11 +966,15 @@ int cdx_colsum_batch_f32(const cdx_colsum_batch* batch, void* hip_stream);
  * Replaces, per update() call, torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW.step() + optimizer.zero_grad() +
  * DiffusionModel.ema_update() (reference diffusion/diffusionsde.py:114-141, diffusion/basic.py:66,83-86): one device table of
  * tensor pointers cut into `chunk_elems`-float chunks, one workgroup per chunk.  AdamW arithmetic = torch/optim/adamw.py's
- * single-tensor path term by term; the host passes step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t).
+ * single-tensor path term by term; the host passes step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t), and (ABI 19) the
+ * complements 1 - beta1, 1 - beta2, 1 - ema_rate rounded to fp32 from their float64 values, as torch rounds the `weight` / `value` /
+ * `alpha` scalars of lerp_ / addcmul_ / add_: 1.f - beta2 formed from the ROUNDED beta2 is off by up to ulp(beta2) / 2 (1 - beta2) --
+ * 1.3e-5 of exp_avg_sq at beta2 = 0.999.
  * ---------------------------------------------------------------------------------------------- */
 #define CDX_OPT_ADAMW 0   /* g*clip; p *= 1-lr*wd; m,v; p -= step_size*m/(sqrt(v)/bc2_sqrt+eps); [ema = r*ema+(1-r)*p]; [g = 0] */
 #define CDX_OPT_EMA 1     /* ema = ema_rate*ema + (1-ema_rate)*p */
-#define CDX_OPT_SUMSQ 2   /* norm[0] = sqrt(sum g^2) (fixed-order reduction), norm[1] = min(1, max_norm/(norm[0]+1e-6)) (1 if max_norm <= 0) */
+#define CDX_OPT_SUMSQ 2   /* norm[0] = sqrt(sum g^2) (fixed-order reduction), norm[1] = min(1, max_norm/(norm[0]+1e-6)) (1 if max_norm <= 0;
+                           * a NaN norm gives a NaN coefficient, as torch's clamp(max = 1) does, an infinite one 0) */
 #define CDX_OPT_ZERO 3    /* g = 0 */
 #define CDX_OPT_ADAM 4    /* ABI 16: as CDX_OPT_ADAMW with torch.optim.Adam's L2 decay -- g = g*clip + wd*p, no decoupled decay -- the optimiser of
                            * the reference's classifiers (classifier/base.py:24) */
@@ -988,6 +992,8 @@ typedef struct cdx_optim_args {
     int32_t zero_grad;        /* AdamW: leave the gradients zeroed */
     float* partial;           /* device [n_chunks]: scratch of the norm pass */
     float* norm;              /* device [2] */
+    float one_minus_beta1, one_minus_beta2;   /* ABI 19: AdamW / Adam, each in (0, 1] */
+    float one_minus_ema_rate;                 /* ABI 19: wherever ema_rate is read */
 } cdx_optim_args;
 int cdx_optim_f32(const cdx_optim_args* args, void* hip_stream);
 

@@ -243,5 +243,7 @@ def test_optimiser_entry_validates_before_touching_the_device(lib):
     a = optim.CdxOptimArgs(n_tensors=1, n_chunks=1, chunk_elems=4096, chunks=8, numel=8, mode=optim.OPT_ADAMW, p=8, g=8, m=8, v=8,
                            beta1=0.9, beta2=0.999, bc2_sqrt=0.0)
     assert lib.cdx_optim_f32(ctypes.byref(a), None) == -1 and b"bc2_sqrt" in lib.cdx_last_error()
+    a.bc2_sqrt = 0.5                                                                                 # ABI 19: the host passes 1 - beta
+    assert lib.cdx_optim_f32(ctypes.byref(a), None) == -1 and b"one_minus_beta1" in lib.cdx_last_error()
     a = optim.CdxOptimArgs(n_tensors=1, n_chunks=1, chunk_elems=4096, chunks=8, numel=8, mode=9)
     assert lib.cdx_optim_f32(ctypes.byref(a), None) == -1 and b"unknown mode" in lib.cdx_last_error()

@@ -334,7 +334,7 @@ def test_cep_validation_fails_loudly():
 
 def test_cep_mirror_has_the_c_layout(tmp_path):
     """``CdxCepStep`` == ``cdx_cep_step`` of include/cdx.h (gcc sizeof / offsetof); the addition is purely additive: the ABI number of
-    header and binding is still 18."""
+    header and binding did not move with it (19 now: cdx_optim_args carries the host-computed 1 - beta complements)."""
     from cleandiffuser_amd.engine import cep, runtime
     src = ['#include <stdio.h>', '#include <stddef.h>', '#include "cdx.h"', 'int main(void){', 'printf("%d\\n", CDX_ABI_VERSION);',
            'printf("%d\\n", CDX_ENERGY_MAX_HIDDEN);', 'printf("%zu\\n", sizeof(cdx_cep_step));']
@@ -345,7 +345,7 @@ def test_cep_mirror_has_the_c_layout(tmp_path):
     exe = tmp_path / "layout"
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)], check=True)
     out = iter(subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split())
-    assert int(next(out)) == runtime.ABI_VERSION == 18
+    assert int(next(out)) == runtime.ABI_VERSION == 19
     assert int(next(out)) == cep.MAX_HIDDEN
     assert int(next(out)) == ctypes.sizeof(cep.CdxCepStep)
     for f in cep.CdxCepStep._fields_:

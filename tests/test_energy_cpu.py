@@ -230,7 +230,7 @@ def test_the_lds_plan_is_a_limit_of_the_route(amd_lib):
 # ------------------------------------------------------------------------------------------------------------------- #
 def test_energy_mirror_has_the_c_layout(tmp_path):
     """``CdxEnergyGuided`` / ``CdxEnergyBlock`` == the structs of include/cdx.h (gcc sizeof / offsetof); the addition is purely additive:
-    the ABI number of header and binding is still 18."""
+    the ABI number of header and binding is 19 (18 until cdx_optim_args gained the host-computed complements; this entry itself was additive)."""
     from cleandiffuser_amd.engine import energy, runtime
     c_name = lambda f: "in" if f == "in_" else f                                     # noqa: E731
     src = ['#include <stdio.h>', '#include <stddef.h>', '#include "cdx.h"', 'int main(void){',
@@ -246,7 +246,7 @@ def test_energy_mirror_has_the_c_layout(tmp_path):
     exe = tmp_path / "layout"
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)], check=True)
     out = iter(subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split())
-    assert int(next(out)) == runtime.ABI_VERSION == 18
+    assert int(next(out)) == runtime.ABI_VERSION == 19
     assert [int(next(out)) for _ in range(3)] == [energy.MAX_STEPS, energy.MAX_BLOCKS, energy.MAX_HIDDEN]
     for _, mirror in pairs:
         assert int(next(out)) == ctypes.sizeof(mirror)

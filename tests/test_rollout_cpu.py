@@ -178,7 +178,7 @@ def test_the_rollout_leaves_the_unets_alone(amd_lib, monkeypatch):
 
 
 def test_rollout_mirror_has_the_c_layout(tmp_path):
-    """``CdxRollout`` == ``cdx_rollout`` of include/cdx.h (gcc sizeof / offsetof), and the ABI number of header and binding is 18."""
+    """``CdxRollout`` == ``cdx_rollout`` of include/cdx.h (gcc sizeof / offsetof), and the ABI number of header and binding is 19."""
     from cleandiffuser_amd.engine import rollout, runtime
     fields = [f[0] for f in rollout.CdxRollout._fields_]
     src = ['#include <stdio.h>', '#include <stddef.h>', '#include "cdx.h"', 'int main(void){',
@@ -190,7 +190,7 @@ def test_rollout_mirror_has_the_c_layout(tmp_path):
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)], check=True)
     out = iter(subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split())
     assert int(next(out)) == ctypes.sizeof(rollout.CdxRollout)
-    assert int(next(out)) == runtime.ABI_VERSION == 18
+    assert int(next(out)) == runtime.ABI_VERSION == 19
     assert int(next(out)) == rollout.MAX_STEPS
     for f in fields:
         assert getattr(rollout.CdxRollout, f).offset == int(next(out)), f

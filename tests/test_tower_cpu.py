@@ -349,8 +349,9 @@ def test_tower_validation_fails_loudly():
 
 
 def test_tower_mirrors_have_the_c_layout(tmp_path):
-    """``CdxTower`` / ``CdxColsumJob`` / ``CdxColsumBatch`` == the structs of include/cdx.h (gcc sizeof / offsetof); the addition is purely
-    additive: the ABI number of the header did not move."""
+    """``CdxTower`` / ``CdxColsumJob`` / ``CdxColsumBatch`` == the structs of include/cdx.h (gcc sizeof / offsetof), and the header's ABI number
+    is the one the package expects (19 since ``cdx_optim_args`` carries the host's 1 - beta complements; the tower's own entries were
+    purely additive)."""
     from cleandiffuser_amd.engine import tower
     mirrors = {"cdx_tower": tower.CdxTower, "cdx_colsum_job": tower.CdxColsumJob, "cdx_colsum_batch": tower.CdxColsumBatch}
     src = ['#include <stdio.h>', '#include <stddef.h>', '#include "cdx.h"', 'int main(void){',
@@ -364,7 +365,7 @@ def test_tower_mirrors_have_the_c_layout(tmp_path):
     exe = tmp_path / "layout"
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)], check=True)
     out = iter(subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split())
-    assert [int(next(out)) for _ in range(3)] == [18, tower.MAX_LAYERS, tower.COLSUM_BATCH]
+    assert [int(next(out)) for _ in range(3)] == [19, tower.MAX_LAYERS, tower.COLSUM_BATCH]
     for cname, mirror in mirrors.items():
         assert int(next(out)) == ctypes.sizeof(mirror), cname
         for f in mirror._fields_:
