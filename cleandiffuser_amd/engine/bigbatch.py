@@ -104,6 +104,16 @@ class CdxChiUNetWeights(ctypes.Structure):
                [("local_obs_dim", _I), ("lc_down_w", _FP), ("lc_down_b", _FP), ("attn", ctypes.POINTER(CdxUnetAttn))]
 
 
+class CdxHcriticBlock(ctypes.Structure):                 # the horizon critic's executor: host path in engine/hcritic.py
+    _fields_ = [(n, _FP) for n in ("qkv_w", "qkv_b", "proj_w", "proj_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")]
+
+
+class CdxHcriticWeights(ctypes.Structure):
+    _fields_ = [("tokens", _I), ("in_dim", _I), ("d_model", _I), ("n_heads", _I), ("depth", _I), ("pre_norm", _I),
+                ("eps", ctypes.c_float), ("x_proj_w", _FP), ("x_proj_b", _FP), ("pos", _FP),
+                ("blocks", ctypes.POINTER(CdxHcriticBlock)), ("fin_w", _FP), ("fin_b", _FP)]
+
+
 _declared = False
 
 

@@ -812,6 +812,22 @@ class _LayerNormAffine(torch.autograd.Function):
         return dx, dg, db, None
 
 
+class _LayerNormPlain(torch.autograd.Function):
+    """nn.LayerNorm(elementwise_affine=False) on (rows, C): ``cdx_layernorm_f32`` / ``cdx_layernorm_bwd_f32`` with no gain."""
+
+    @staticmethod
+    def forward(ctx, x, eps):
+        x = x.contiguous()
+        ctx.save_for_backward(x)
+        ctx.eps = eps
+        return blocks.layernorm(x, eps=eps)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        return blocks.layernorm_backward(dy.contiguous(), x, eps=ctx.eps), None
+
+
 class _LayerNormMod(torch.autograd.Function):
     """adaLN: LayerNorm(x) (no affine) * (1 + scale[b]) + shift[b] over `tokens` rows per sample (reference dit.py:10-11,33-35,48).
     scale / shift: (B, C) views of one modulation tensor (same row stride)."""

@@ -1,7 +1,9 @@
 """Value heads the pipelines evaluate on freshly sampled tensors: the candidate re-weighting critics ``DQLCritic`` and
 IQL's ``TwinQ`` / ``V``.  Interface / checkpoint contract: reference utils/building_blocks.py:79-147 and utils/iql.py:7-95 (same
-attribute names, hence the same ``state_dict`` keys).  Diffusion Veteran's horizon critic and the reference's transformer toolkit
-(building_blocks.py:149-373) are outside the sampling path and are not mirrored.
+attribute names, hence the same ``state_dict`` keys).  Decision Veteran's horizon critic ``DVHorizonCritic`` (building_blocks.py:149-229),
+which the veteran_d4rl_* pipelines evaluate on every environment step's candidate plans, is mirrored with a native scoring call
+(engine/hcritic.py); it is imported from this module -- ``cleandiffuser_amd.utils`` does not re-export it.
+The reference's generic transformer toolkit (``Transformer`` / ``MultiHeadAttention``, building_blocks.py:231-373) is not mirrored.
 
 Execution: every head here is a chain of ``Linear -> [LayerNorm] -> activation`` over rows, so on a ROCm device without
 autograd the chain runs through ``engine/heads.py`` (fp32-MFMA GEMM with fused bias/activation epilogue + one fused
@@ -107,6 +109,71 @@ class V(nn.Module):
 
 IDQLQNet = TwinQ
 IDQLVNet = V
+
+
+class DVTransformerBlock(nn.Module):
+    """One block of the horizon critic: self-attention and a GELU(tanh) MLP around two LayerNorms without gain or shift.  "post":
+    x = norm1(x + attn(x)); x = norm2(x + mlp(x)).  "pre": x = norm1(x); x = x + attn(x); x = x + mlp(norm2(x)) -- the residual stream
+    continues from the normalised tensor."""
+
+    def __init__(self, hidden_size: int, n_heads: int, dropout: float = 0.0, norm_type: str = "post"):
+        super().__init__()
+        self.norm_type = norm_type
+        self.norm1 = nn.LayerNorm(hidden_size, elementwise_affine=False, eps=1e-6)
+        self.attn = nn.MultiheadAttention(hidden_size, n_heads, dropout, batch_first=True)
+        self.norm2 = nn.LayerNorm(hidden_size, elementwise_affine=False, eps=1e-6)
+        self.mlp = nn.Sequential(nn.Linear(hidden_size, hidden_size * 4), nn.GELU(approximate="tanh"), nn.Dropout(dropout),
+                                 nn.Linear(hidden_size * 4, hidden_size))
+
+    def forward(self, x):
+        if self.norm_type == "post":
+            x = self.norm1(x + self.attn(x, x, x)[0])
+            return self.norm2(x + self.mlp(x))
+        if self.norm_type == "pre":
+            x = self.norm1(x)
+            x = x + self.attn(x, x, x)[0]
+            return x + self.mlp(self.norm2(x))
+        raise NotImplementedError(f"norm_type {self.norm_type!r}")
+
+
+class DVHorizonCritic(nn.Module):
+    """Decision Veteran's horizon critic: a transformer over the tokens of a plan (b, T, in_dim) whose value (b, 1) is read off token 0.
+    ``emb_dim`` is part of the constructor's contract and otherwise unused.  Execution (engine/hcritic.py): without autograd on a ROCm
+    device the executor ``cdx_hcritic_run`` where it is switched on, with autograd the library's nodes where they are, else the stock
+    modules below (DESIGN.md 3n says which is the default and why)."""
+
+    def __init__(self, in_dim: int, emb_dim: int, d_model: int = 384, n_heads: int = 6, depth: int = 12, dropout: float = 0.0,
+                 norm_type: str = "post"):
+        super().__init__()
+        self.in_dim, self.emb_dim, self.d_model, self.dropout = in_dim, emb_dim, d_model, dropout
+        from .embeddings import SinusoidalEmbedding
+        self.x_proj = nn.Linear(in_dim, d_model)
+        self.pos_emb = SinusoidalEmbedding(d_model)
+        self.pos_emb_cache = None
+        self.blocks = nn.ModuleList([DVTransformerBlock(d_model, n_heads, dropout, norm_type) for _ in range(depth)])
+        self.final_layer = nn.Linear(d_model, 1)
+        for m in self.modules():
+            if isinstance(m, nn.Linear):
+                nn.init.xavier_uniform_(m.weight)
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
+
+    def _positions(self, tokens: int, device) -> torch.Tensor:
+        if self.pos_emb_cache is None or self.pos_emb_cache.shape[0] != tokens or self.pos_emb_cache.device != device:
+            self.pos_emb_cache = self.pos_emb(torch.arange(tokens, device=device))
+        return self.pos_emb_cache
+
+    def forward(self, x):
+        from ..engine import hcritic
+        y = hcritic.try_score(self, x)                 # scoring sampled plans: one executor call
+        if y is not None:
+            return y
+        if hcritic.supports_nodes(self, x):            # the critic's own training step: library nodes forward and backward
+            return hcritic.forward_nodes(self, x)
+        x = self.x_proj(x) + self._positions(x.shape[1], x.device)[None]
+        for block in self.blocks:
+            x = block(x)
+        return self.final_layer(x)[:, 0, :]
 
 
 class IQL(nn.Module):

@@ -962,6 +962,43 @@ typedef struct cdx_colsum_batch {
 int cdx_colsum_batch_f32(const cdx_colsum_batch* batch, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Decision Veteran's horizon critic in ONE call (csrc/cdx_hcritic.hip).  Purely additive entries: no existing struct or call
+ * changes, so CDX_ABI_VERSION stays 19.  Reference: utils/building_blocks.py:149-229 (DVTransformerBlock / DVHorizonCritic), scored on
+ * num_envs x planner_num_candidates freshly sampled plans at every environment step of pipelines/veteran_d4rl_{kitchen,antmaze,maze2d}.py.
+ *   h = x_proj(x) + pos;  per block, with u = LN(h) (pre-norm) or u = h (post-norm):
+ *   a = out_proj(attention(in_proj(u))) + u;  v = LN(a);  o = fc2(gelu_tanh(fc1(v))) + (pre-norm: a | post-norm: v);
+ *   h = o (pre-norm) or LN(o) (post-norm);  out[b] = final(h)[b, token 0].   LN: no gain / shift, `eps`.
+ * Only token 0 of the last block reaches `out`: blocks 0 .. depth - 2 run over all rows; in the last one all rows go through the key /
+ * value projection only (rows [d, 3d) of in_proj), the query (rows [0, d)) takes the token-0 rows in place (lda = tokens * d), a
+ * single-query attention kernel (one wave64 per (trajectory, head); no atomics, one fixed lane and order per element: bit-reproducible)
+ * forms the one attended row, and everything behind it runs on `chunk` rows.  Every Linear is one cdx_gemm_f32 launch with its epilogue.
+ * Device pointers in the checkpoint's own PyTorch layouts; `blocks` is a HOST array.  The batch is processed in independent passes of
+ * `chunk` trajectories (0: the library chooses).  Caller-owned workspace, caller's stream, no allocation, no synchronisation.
+ * Limits (CDX_EINVAL with a message, before anything is launched): 1 <= tokens <= 64; d_model % n_heads == 0, head dimension <= 64,
+ * d_model <= 1024; depth >= 1; in_dim >= 1; a pass of at most 2^31 - 1 floats in its widest buffer.  batch == 0 is CDX_OK.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct cdx_hcritic_block {
+    const float *qkv_w, *qkv_b;       /* attn.in_proj_weight (3d, d), in_proj_bias (3d) */
+    const float *proj_w, *proj_b;     /* attn.out_proj (d, d) */
+    const float *fc1_w, *fc1_b;       /* mlp.0 (4d, d) */
+    const float *fc2_w, *fc2_b;       /* mlp.3 (d, 4d) */
+} cdx_hcritic_block;
+typedef struct cdx_hcritic_weights {
+    int32_t tokens, in_dim, d_model, n_heads, depth;
+    int32_t pre_norm;                 /* 1: norm_type "pre", 0: "post" */
+    float eps;
+    const float *x_proj_w, *x_proj_b; /* (d, in_dim), (d) */
+    const float* pos;                 /* (tokens, d): the positional table */
+    const cdx_hcritic_block* blocks;  /* HOST array [depth] of device pointers */
+    const float *fin_w, *fin_b;       /* final_layer (1, d), (1) */
+} cdx_hcritic_weights;
+/* floats of workspace a run of `batch` trajectories in passes of `chunk` needs, or a negative CDX_E* code outside the limits */
+long long cdx_hcritic_workspace_floats(const cdx_hcritic_weights* w, int32_t batch, int32_t chunk);
+/* x (batch, tokens, in_dim) -> out (batch) */
+int cdx_hcritic_run(const cdx_hcritic_weights* w, const float* x, float* out, int32_t batch, int32_t chunk, float* workspace,
+                    long long workspace_floats, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimiser side of DiffusionModel.update(): multi-tensor AdamW + EMA + gradient-norm clipping.
  * Replaces, per update() call, torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW.step() + optimizer.zero_grad() +
  * DiffusionModel.ema_update() (reference diffusion/diffusionsde.py:114-141, diffusion/basic.py:66,83-86): one device table of
