@@ -316,7 +316,10 @@ __global__ __launch_bounds__(256) void cdx_mha_train_kernel(const cdx_mha_train_
             sacc = fmaf(Q(i, d), K(j, d), sacc);
             if (BWD) pacc = fmaf(dO(i, d), V(j, d), pacc);
         }
-        P(i, j) = sacc * a.scale + (a.mask ? a.mask[i * Tk + j] : 0.f);
+        // clamped like the sampling attention kernels (cdx_gemm.hip): masks arrive with -inf or with the finite floor finfo(float).min
+        // (engine/bigbatch.py), and a row whose entries ALL sit at the floor must come out uniform, as torch's softmax gives it --
+        // unclamped, every exp(-3.4e38 - (-3.0e38)) of such a row was 0 and the row 0 x inf
+        P(i, j) = fmaxf(sacc * a.scale + (a.mask ? a.mask[i * Tk + j] : 0.f), -3.0e38f);
         if (BWD) dP(i, j) = pacc;
     }
     __syncthreads();

@@ -448,11 +448,15 @@ def attention_backward(qkv: torch.Tensor, dout: torch.Tensor, batch: int, tokens
 
 
 def mha_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, batch: int, n_heads: int, mask: Optional[torch.Tensor] = None,
-              keep: Optional[torch.Tensor] = None, dout: Optional[torch.Tensor] = None, grads=None):
+              keep: Optional[torch.Tensor] = None, dout: Optional[torch.Tensor] = None, grads=None,
+              out: Optional[torch.Tensor] = None):
     """The attention core of nn.MultiheadAttention in training (``cdx_mha_train_fwd_f32`` / ``_bwd_f32``): q (batch * Tq, dm), k / v
     (batch * Tk, dm) -- column blocks of packed projections welcome --, additive `mask` (Tq, Tk), dropout `keep` (batch, n_heads, Tq,
-    Tk) of 0 | 1 / (1 - p).  Without `dout`: the output (batch * Tq, dm); with it: (dq, dk, dv) -- written into `grads` (three
-    2-D views, e.g. the column blocks of one packed gradient) when given, else three fresh tensors."""
+    Tk) of 0 | 1 / (1 - p).  Without `dout`: the output (batch * Tq, dm), written into `out` (contiguous) when given; with it: (dq, dk,
+    dv) -- written into `grads` (three 2-D views, e.g. the column blocks of one packed gradient) when given, else three fresh tensors.
+    Mask entries may be -inf or the finite floor ``finfo(float32).min`` that engine/bigbatch.py clamps masks to: scores are clamped at
+    -3.0e38 as in the sampling attention kernels, so a query row whose entries ALL sit at the floor gives the uniform row 1 / Tk, as
+    torch does.  A row masked entirely with true -inf is outside the contract (torch returns NaN there)."""
     dm = q.shape[1]
     tq, tk, dh = q.shape[0] // batch, k.shape[0] // batch, dm // n_heads
     assert q.shape[0] == batch * tq and k.shape == v.shape == (batch * tk, dm) and dh * n_heads == dm
@@ -463,7 +467,9 @@ def mha_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, batch: int, n_h
     a = CdxMhaTrainArgs(q=q.data_ptr(), k=k.data_ptr(), v=v.data_ptr(), mask=_p(mask), keep=_p(keep), B=batch, Tq=tq, Tk=tk, n_heads=n_heads,
                         head_dim=dh, ldq=_rows(q), ldk=_rows(k), ldv=_rows(v), ldo=dm, scale=float(dh) ** -0.5)
     if dout is None:
-        out = torch.empty((batch * tq, dm), device=q.device, dtype=torch.float32)
+        if out is None:
+            out = torch.empty((batch * tq, dm), device=q.device, dtype=torch.float32)
+        assert out.shape == (batch * tq, dm) and out.is_contiguous() and out.dtype == torch.float32
         a.out = out.data_ptr()
         _check(_lib().cdx_mha_train_fwd_f32(ctypes.byref(a), _stream_ptr(q.device)), "cdx_mha_train_fwd_f32")
         return out

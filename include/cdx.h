@@ -382,7 +382,9 @@ int cdx_attention_bwd_f32(const cdx_attn_bwd_args* args, void* hip_stream);
  * reference runs through nn.TransformerDecoderLayer / nn.TransformerEncoderLayer in train mode (nn_diffusion/chitransformer.py:108-121,
  * 148-154: causal self-attention, staggered memory cross-attention, attention dropout 0.3) and through nn.MultiheadAttention in
  * dit.py:20,34.  The backward recomputes P from the forward's operands: dq (B * Tq, lddq), dk / dv (B * Tk, lddk / lddv).
- * Tq, Tk <= 64, head_dim <= 64; every row of `mask` must allow at least one key. */
+ * Tq, Tk <= 64, head_dim <= 64.  Scores are clamped at -3.0e38 as in the sampling attention kernels: a row of `mask` whose entries all
+ * sit at the finite floor -FLT_MAX (-3.4e38, what the host clamps -inf to) gives the uniform row 1 / Tk, as torch does;
+ * a row that is -inf throughout is outside the contract (torch returns NaN there). */
 typedef struct cdx_mha_train_args {
     const float* q;
     const float* k;

@@ -1530,10 +1530,14 @@ def test_layernorm_and_attention_backward_kernels_match_autograd():
         torch.testing.assert_close(got, qkv.grad, rtol=2e-4, atol=2e-5)
 
 
-@pytest.mark.parametrize("M,C,T,blocks_of", [(66, 1500, 33, None), (66, 1500, 33, 1536), (40, 320, 10, 400), (24, 2050, 8, 2100), (35, 1023, 7, None)])
+@pytest.mark.parametrize("M,C,T,blocks_of", [(66, 1500, 33, None), (66, 1500, 33, 1536), (40, 320, 10, 400), (24, 2050, 8, 2100), (35, 1023, 7, None),
+                                             (6, 1, 3, None), (6, 1, 3, 9), (6, 63, 3, 70), (6, 65, 3, None), (6, 1024, 3, 1031),
+                                             (6, 1025, 3, None), (6, 2048, 3, None), (6, 2049, 3, 2057)])
 def test_layernorm_backward_against_float64_on_column_blocks(M, C, T, blocks_of):
     """cdx_layernorm_bwd_f32 against float64 autograd ON THE CPU: the <32> variant (1024 < C <= 2048), odd widths, and dy / x as column
-    blocks of wider matrices (lddy != C, ldx != C, first column 3: no alignment to lean on)."""
+    blocks of wider matrices (lddy != C, ldx != C, first column 3: no alignment to lean on).  M = 6: the widths at which the launcher
+    changes instantiation (1024 | 1025, 2048 | 2049), one column short of / past a wave's 64 lanes, and a row of ONE column (xhat = 0,
+    dx = 0), each on two rows more than a workgroup's four, contiguous or as a column block."""
     import torch.nn.functional as F
     from cleandiffuser_amd.engine import blocks
     g = torch.Generator().manual_seed(M + C)
