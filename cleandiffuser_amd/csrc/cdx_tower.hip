@@ -14,7 +14,7 @@
 // H_l, P_l, rstd_l (forward) and G_l = dz, Sb, Sg (backward) go to global memory: the weight and bias sums over the rows are the caller's
 // (one cdx_conv_wgrad_batch_f32), the gain and shift sums over the tiles one cdx_colsum_batch_f32 (below).  Rows of the last tile past R
 // carry a zero gradient and nothing is written for them.  No atomics in the two tower kernels, every element is produced by one fixed
-// lane in one fixed order: bit-reproducible.
+// lane in one fixed order: bit-reproducible.  The forward's per-layer body lives in cdx_tower_layers.h, which cdx_select.hip runs too.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -22,6 +22,7 @@
 #include "../../include/cdx.h"
 #include "cdx_act.h"
 #include "cdx_rowtile.h"
+#include "cdx_tower_layers.h"
 
 namespace {
 
@@ -40,15 +41,6 @@ struct TowerArgs {
 };
 static_assert(sizeof(TowerArgs) <= 4096, "the kernel argument segment holds 4 KiB");
 
-__device__ __forceinline__ float tw_act(int act, float y) {
-    switch (act) {
-        case CDX_ACT_MISH: return cdx_act_mish(y);
-        case CDX_ACT_SILU: return cdx_act_silu(y);
-        case CDX_ACT_RELU: return cdx_act_relu(y);
-        case CDX_ACT_TANH: return cdx_act_tanh(y);
-        default: return y;
-    }
-}
 __device__ __forceinline__ float tw_act_grad(int act, float y) {
     switch (act) {
         case CDX_ACT_MISH: return cdx_act_mish_grad(y);
@@ -58,77 +50,37 @@ __device__ __forceinline__ float tw_act_grad(int act, float y) {
         default: return 1.0f;
     }
 }
-// the sum over the 16 lanes of a row (tid >> 4): a butterfly, the same bits in every lane
-__device__ __forceinline__ float tw_sum16(float v) {
-    v += __shfl_xor(v, 8, 16);
-    v += __shfl_xor(v, 4, 16);
-    v += __shfl_xor(v, 2, 16);
-    v += __shfl_xor(v, 1, 16);
-    return v;
-}
+// what the forward writes to global memory for the live rows of its tile: the last layer's h to out, and with `save` H_l, P_l, rstd_l
+struct TowerSave {
+    const cdx_tower& g;
+    const TowerPlan& p;
+    int t;
+    long long R, row0;
+    __device__ void element(int l, int r, int c, float h, float pre) const {
+        if (row0 + r >= R) return;
+        const int W = g.width[l];
+        const size_t at = (size_t)(row0 + r) * W + c;
+        if (l == g.n_layers - 1) g.out[t][at] = h;
+        else if (g.save) (g.H[t] + (size_t)R * p.off_col[l])[at] = h;
+        if (g.save) (g.P[t] + (size_t)R * p.off_col[l])[at] = pre;
+    }
+    __device__ void row_rstd(int l, int r, float rstd) const {
+        if (row0 + r < R && g.save) g.rstd[t][(size_t)l * R + (row0 + r)] = rstd;
+    }
+};
 
 __global__ __launch_bounds__(256) void cdx_tower_fwd_kernel(const TowerArgs a) {
     extern __shared__ __attribute__((aligned(16))) float tw_lds[];
     const cdx_tower& g = a.g;
     const TowerPlan& p = a.p;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int t = blockIdx.y, L = g.n_layers, ld = p.ld;
+    const int t = blockIdx.y, ld = p.ld;
     const long long R = g.R, row0 = (long long)blockIdx.x * RO_ROWS;
-    const int rr = tid >> 4, sub = tid & 15;          // the norm's view: 16 lanes per row
-    const bool live = row0 + rr < R;
     auto image = [&](int i) { return tw_lds + (size_t)i * RO_ROWS * ld; };
 
     ro_load_rows(image(0), ld, ro_r16(g.K0), g.x, g.K0, row0, R, tid, [](long long row) { return row; });
     __syncthreads();
-    int src = 0;
-    for (int l = 0; l < L; ++l) {
-        const int W = g.width[l], K = l ? g.width[l - 1] : g.K0, act = g.act[l];
-        const float* bias = g.b[t][l];
-        float* dst = image(src ^ 1);
-        float* Hl = l == L - 1 ? g.out[t] : (g.save ? g.H[t] + (size_t)R * p.off_col[l] : nullptr);
-        float* Pl = g.save ? g.P[t] + (size_t)R * p.off_col[l] : nullptr;
-        if (!g.norm[l]) {
-            ro_product<false>(image(src), ld, g.w[t][l], K, W, K, lane, wave, [&](int r, int n, float v) {
-                const float z = v + bias[n];
-                const float h = tw_act(act, z);
-                dst[r * ld + n] = h;
-                if (row0 + r < R) {
-                    const size_t at = (size_t)(row0 + r) * W + n;
-                    if (Hl) Hl[at] = h;
-                    if (Pl) Pl[at] = z;
-                }
-            });
-            __syncthreads();
-        } else {
-            ro_product<false>(image(src), ld, g.w[t][l], K, W, K, lane, wave, [&](int r, int n, float v) { dst[r * ld + n] = v + bias[n]; });
-            __syncthreads();
-            const float* gamma = g.gamma[t][l];
-            const float* beta = g.beta[t][l];
-            float* zr = dst + rr * ld;
-            float s = 0.f;
-            for (int c = sub; c < W; c += 16) s += zr[c];
-            const float mean = tw_sum16(s) / (float)W;
-            float q = 0.f;
-            for (int c = sub; c < W; c += 16) {
-                const float d = zr[c] - mean;
-                q += d * d;
-            }
-            const float rstd = 1.0f / sqrtf(tw_sum16(q) / (float)W + g.eps[l]);
-            for (int c = sub; c < W; c += 16) {
-                const float xhat = (zr[c] - mean) * rstd;
-                const float h = tw_act(act, xhat * gamma[c] + beta[c]);
-                zr[c] = h;
-                if (live) {
-                    const size_t at = (size_t)(row0 + rr) * W + c;
-                    if (Hl) Hl[at] = h;
-                    if (Pl) Pl[at] = xhat;
-                }
-            }
-            if (sub == 0 && live && g.save) g.rstd[t][(size_t)l * R + (row0 + rr)] = rstd;
-            __syncthreads();
-        }
-        src ^= 1;
-    }
+    tw_forward_layers(g, t, g.K0, image(0), ld, image(1), image(0), ld, tid, lane, wave, TowerSave{g, p, t, R, row0});
 }
 
 __global__ __launch_bounds__(256) void cdx_tower_bwd_kernel(const TowerArgs a) {
@@ -247,24 +199,14 @@ int tower_plan(const char* who, const cdx_tower* g, TowerPlan* p) {
     if (!g) return fail("null request");
     if (g->R < 0 || g->R > 0x7fffffff - RO_ROWS) return fail("bad size: R");
     if (g->n_towers != 1 && g->n_towers != 2) return fail("n_towers must be 1 or 2");
-    if (g->n_layers < 1 || g->n_layers > CDX_TOWER_MAX_LAYERS) return fail("n_layers must be 1 .. CDX_TOWER_MAX_LAYERS");
     if (g->K0 <= 0 || g->K0 > RO_MAX_WIDTH) return fail("K0 must be 1 .. 512");
-    int maxw = ro_r16(g->K0), cols = 0;
-    for (int l = 0; l < CDX_TOWER_MAX_LAYERS; ++l) p->off_col[l] = 0;
-    for (int l = 0; l < g->n_layers; ++l) {
-        const int w = g->width[l];
-        if (l == g->n_layers - 1) {
-            if (w <= 0 || w > RO_MAX_X) return fail("the last width must be 1 .. 64");
-        } else if (w <= 0 || w % 16 != 0 || w > RO_MAX_WIDTH) {
-            return fail("every width but the last must be a multiple of 16, at most 512");
-        }
-        const int a = g->act[l];
-        if (a != CDX_ACT_NONE && a != CDX_ACT_MISH && a != CDX_ACT_SILU && a != CDX_ACT_RELU && a != CDX_ACT_TANH)
-            return fail("activation must be none, mish, silu, relu or tanh");
-        if (g->norm[l] && !(g->eps[l] > 0.f)) return fail("eps must be positive");
-        maxw = ro_r16(w) > maxw ? ro_r16(w) : maxw;
-        p->off_col[l] = cols;
-        cols += w;
+    int maxw = 0, cols = 0;
+    const int rc = tw_check_layers(g->n_layers, g->width, g->norm, g->act, g->eps, &maxw, fail);
+    if (rc != CDX_OK) return rc;
+    maxw = ro_r16(g->K0) > maxw ? ro_r16(g->K0) : maxw;
+    for (int l = 0; l < CDX_TOWER_MAX_LAYERS; ++l) {
+        p->off_col[l] = l < g->n_layers ? cols : 0;
+        cols += l < g->n_layers ? g->width[l] : 0;
     }
     p->ld = maxw + 4;
     p->total = 2 * RO_ROWS * p->ld;

@@ -1,4 +1,4 @@
-"""The Python face of csrc/cdx_rowtile.h, shared by the bindings of the row-tile kernels (engine/rollout.py, energy.py, cep.py, tower.py): the tile
+"""The Python face of csrc/cdx_rowtile.h, shared by the bindings of the row-tile kernels (engine/rollout.py, energy.py, cep.py, tower.py, select.py): the tile
 constants, ctypes prototypes, the solver step of the torch restatements and the admission checks that only look at solver and plan."""
 from typing import Optional
 

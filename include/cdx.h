@@ -964,6 +964,80 @@ typedef struct cdx_colsum_batch {
 int cdx_colsum_batch_f32(const cdx_colsum_batch* batch, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Score K candidates per state and pick among them (csrc/cdx_select.hip).  Purely additive entries: no existing struct or call
+ * changes, so CDX_ABI_VERSION stays 19.  Reference: the tail behind ``sample()`` of every value-guided pipeline --
+ * pipelines/idql_d4rl_mujoco.py:181-194, dql_d4rl_mujoco.py:192-200, sfbc_d4rl_mujoco.py:116-120 and :192-196,
+ * qgpo_d4rl_mujoco.py:141-144 and :190-194, veteran_d4rl_mujoco.py:440-446 and :474-478: a critic on the repeated observation next to
+ * the candidates, then softmax / multinomial / argmax / argsort and a gather.
+ * S states own K consecutive rows each (row s K + k is candidate k of state s).
+ *   cdx_select_f32        the reduction over given scores (S K): one workgroup of one wave64 per state, the state's scores in LDS.
+ *                         x_k = temperature score_k, w_k = exp(x_k - max x) / sum_j exp(x_j - max x).  Written where the pointer is
+ *                         non-null: weights (S, K) = w; value (S) = sum_k w_k score_k; index (S, n) int32 and picked (S, P), n = top_k
+ *                         in CDX_SELECT_TOPK_MEAN and 1 otherwise:
+ *                           CDX_SELECT_NONE       weights and value only (index and picked must be NULL);
+ *                           CDX_SELECT_ARGMAX     the first maximum of the scores;
+ *                           CDX_SELECT_SAMPLE     the smallest k whose running sum w_0 + .. + w_k, taken in index order, exceeds u[s]
+ *                                                 (one caller-drawn uniform in [0, 1) per state); k = K - 1 catches what is left;
+ *                           CDX_SELECT_TOPK_MEAN  top_k passes of "the largest score not yet taken, the lowest index on ties": index holds
+ *                                                 them in rank order, picked the mean of their payload rows summed in rank order.
+ *                         picked = the chosen row of `payload` (S K rows of P floats, row stride payload_ld >= P: a slice such as
+ *                         traj[:, 0, obs_dim:] needs no copy).  Every sum runs in one fixed order (lane j adds its k = j, j + 64, .. in
+ *                         order, a fixed butterfly combines the 64 lanes); no atomics; no workgroup waits for another: bit-reproducible.
+ *   cdx_score_select_f32  the critic in front of it: one or two towers of the same shape (the layers of cdx_tower, the last width 1) over
+ *                         the rows [obs_s | cand_row], K0 = O + A, `obs` (S, O) NOT repeated (NULL with O == 0: a critic over the
+ *                         candidates alone).  Grid S * ceil(K / 16) workgroups of 4 wave64: a 16-row tile never straddles two states,
+ *                         the observation row is read once per tile and broadcast into the LDS image, rows of a ragged last tile past K
+ *                         write nothing and take no part in any reduction.  The workgroup runs tower 0, then tower 1, on the same
+ *                         image, keeps the element-wise minimum (a NaN stays) and writes scores (S K).  With K <= 16 a state is one
+ *                         tile and the same workgroup goes on to the reduction of cdx_select_f32 on `sel` (sel.scores is not read;
+ *                         sel.S, sel.K are the sizes of the call): ONE launch.  With K > 16 the call writes scores only and `sel`'s
+ *                         outputs are the caller's to fill with a cdx_select_f32 behind it.
+ * Caller-owned memory, one kernel per call enqueued on `hip_stream`, no synchronisation, no allocation.
+ * Limits (CDX_EINVAL with a message, before anything is launched): 1 <= K <= 1024; S K <= 2^31 - 17; P <= 64 and payload_ld >= P;
+ * 1 <= top_k <= min(K, 16) in CDX_SELECT_TOPK_MEAN; temperature finite; u required in CDX_SELECT_SAMPLE; 1 <= A <= 64; O + A <= 512;
+ * the towers within the limits of cdx_tower and their last width 1.  S == 0 is CDX_OK.
+ * ---------------------------------------------------------------------------------------------- */
+#define CDX_SELECT_NONE 0
+#define CDX_SELECT_ARGMAX 1
+#define CDX_SELECT_SAMPLE 2
+#define CDX_SELECT_TOPK_MEAN 3
+#define CDX_SELECT_MAX_K 1024
+#define CDX_SELECT_MAX_TOPK 16
+typedef struct cdx_select {
+    int32_t S, K;
+    int32_t P, payload_ld;                              /* width of a payload row and its stride, in floats */
+    int32_t mode, top_k;                                /* CDX_SELECT_*; top_k is read in CDX_SELECT_TOPK_MEAN only */
+    float temperature;
+    int32_t reserved;
+    const float* scores;                                /* (S K) */
+    const float* payload;                               /* (S K rows, P), NULL when picked is */
+    const float* u;                                     /* (S), CDX_SELECT_SAMPLE */
+    float* weights;                                     /* (S, K) or NULL */
+    float* value;                                       /* (S) or NULL */
+    int32_t* index;                                     /* (S, n) or NULL */
+    float* picked;                                      /* (S, P) or NULL */
+} cdx_select;
+typedef struct cdx_score_select {
+    cdx_select sel;
+    int32_t O, A, n_towers, n_layers;
+    int32_t width[CDX_TOWER_MAX_LAYERS];
+    int32_t norm[CDX_TOWER_MAX_LAYERS];
+    int32_t act[CDX_TOWER_MAX_LAYERS];
+    float eps[CDX_TOWER_MAX_LAYERS];
+    const float* obs;                                   /* (S, O) or NULL */
+    const float* cand;                                  /* (S K, A) */
+    const float* w[2][CDX_TOWER_MAX_LAYERS];            /* as cdx_tower */
+    const float* b[2][CDX_TOWER_MAX_LAYERS];
+    const float* gamma[2][CDX_TOWER_MAX_LAYERS];
+    const float* beta[2][CDX_TOWER_MAX_LAYERS];
+    float* scores;                                      /* (S K) */
+} cdx_score_select;
+int cdx_select_f32(const cdx_select* g, void* hip_stream);
+/* bytes of LDS one workgroup of this request needs, or a negative CDX_E* code when the sizes are out of range */
+long long cdx_score_select_lds_bytes(const cdx_score_select* g);
+int cdx_score_select_f32(const cdx_score_select* g, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Decision Veteran's horizon critic in ONE call (csrc/cdx_hcritic.hip).  Purely additive entries: no existing struct or call
  * changes, so CDX_ABI_VERSION stays 19.  Reference: utils/building_blocks.py:149-229 (DVTransformerBlock / DVHorizonCritic), scored on
  * num_envs x planner_num_candidates freshly sampled plans at every environment step of pipelines/veteran_d4rl_{kitchen,antmaze,maze2d}.py.
