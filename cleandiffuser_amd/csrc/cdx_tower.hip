@@ -10,7 +10,8 @@
 //             centred values over the row in LDS (two passes, a fixed butterfly), xhat = (z - mean) rstd, y = xhat gamma + beta; h = act(y);
 //   backward  per layer from the top: y from the saved P_l (xhat or z), dy = dH act'(y), with a norm g = dy gamma,
 //             dz = rstd (g - mean(g) - xhat mean(g xhat)) and the tile's column sums of dy and dy xhat (rows in order), then
-//             dH_{l-1} = dz W_l on the live weight (ro_product<true>); at layer 0 that is g_x.
+//             dH_{l-1} = dz W_l on the live weight (ro_product<true>); at layer 0 that is g_x.  (tw_backward_layers of cdx_tower_layers.h,
+//             which cdx_critic_step.hip runs too.)
 // H_l, P_l, rstd_l (forward) and G_l = dz, Sb, Sg (backward) go to global memory: the weight and bias sums over the rows are the caller's
 // (one cdx_conv_wgrad_batch_f32), the gain and shift sums over the tiles one cdx_colsum_batch_f32 (below).  Rows of the last tile past R
 // carry a zero gradient and nothing is written for them.  No atomics in the two tower kernels, every element is produced by one fixed
@@ -41,15 +42,6 @@ struct TowerArgs {
 };
 static_assert(sizeof(TowerArgs) <= 4096, "the kernel argument segment holds 4 KiB");
 
-__device__ __forceinline__ float tw_act_grad(int act, float y) {
-    switch (act) {
-        case CDX_ACT_MISH: return cdx_act_mish_grad(y);
-        case CDX_ACT_SILU: return cdx_act_silu_grad(y);
-        case CDX_ACT_RELU: return cdx_act_relu_grad(y);
-        case CDX_ACT_TANH: return cdx_act_tanh_grad(y);
-        default: return 1.0f;
-    }
-}
 // what the forward writes to global memory for the live rows of its tile: the last layer's h to out, and with `save` H_l, P_l, rstd_l
 struct TowerSave {
     const cdx_tower& g;
@@ -66,6 +58,35 @@ struct TowerSave {
     }
     __device__ void row_rstd(int l, int r, float rstd) const {
         if (row0 + r < R && g.save) g.rstd[t][(size_t)l * R + (row0 + r)] = rstd;
+    }
+};
+
+// what the backward reads of the forward's buffers, and where its results go
+struct TowerSaved {
+    const cdx_tower& g;
+    const TowerPlan& plan;
+    int t;
+    long long R, row0;
+    __device__ float p(int l, int r, int c) const {
+        return row0 + r < R ? (g.P[t] + (size_t)R * plan.off_col[l])[(size_t)(row0 + r) * g.width[l] + c] : 0.f;
+    }
+    __device__ float rstd(int l, int r) const { return row0 + r < R ? g.rstd[t][(size_t)l * R + (row0 + r)] : 0.f; }
+};
+struct TowerGrads {
+    const cdx_tower& g;
+    const TowerPlan& p;
+    int t;
+    long long R, row0, tiles, tile;
+    __device__ void element(int l, int r, int c, float dz) const {
+        if (row0 + r < R) (g.G[t] + (size_t)R * p.off_col[l])[(size_t)(row0 + r) * g.width[l] + c] = dz;
+    }
+    __device__ void sums(int l, int c, float sb, float sg) const {
+        const size_t at = (size_t)tiles * p.off_col[l] + (size_t)tile * g.width[l] + c;
+        g.Sb[t][at] = sb;
+        g.Sg[t][at] = sg;
+    }
+    __device__ void gx(int r, int n, float v) const {
+        if (row0 + r < R) g.g_x[t][(size_t)(row0 + r) * g.K0 + n] = v;
     }
 };
 
@@ -89,84 +110,14 @@ __global__ __launch_bounds__(256) void cdx_tower_bwd_kernel(const TowerArgs a) {
     const TowerPlan& p = a.p;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int t = blockIdx.y, L = g.n_layers, ld = p.ld;
-    const long long R = g.R, row0 = (long long)blockIdx.x * RO_ROWS, tiles = gridDim.x;
-    const int rr = tid >> 4, sub = tid & 15;
-    const long long row = row0 + rr;
-    const bool live = row < R;
+    const long long R = g.R, row0 = (long long)blockIdx.x * RO_ROWS;
     auto image = [&](int i) { return tw_lds + (size_t)i * RO_ROWS * ld; };
 
     const int WL = g.width[L - 1];
     ro_load_rows(image(0), ld, ro_r16(WL), g.g_out[t], WL, row0, R, tid, [](long long r) { return r; });
     __syncthreads();
-    int cur = 0;
-    for (int l = L - 1; l >= 0; --l) {
-        const int W = g.width[l], K = l ? g.width[l - 1] : g.K0, act = g.act[l];
-        float* d = image(cur);                        // dH_l, then dy, then dz: the A operand of the transposed product
-        float* o = image(cur ^ 1);                    // xhat of a normed layer, then dH_{l-1}
-        const float* Pl = g.P[t] + (size_t)R * p.off_col[l];
-        float* Gl = g.want_params ? g.G[t] + (size_t)R * p.off_col[l] : nullptr;
-        float* dr = d + rr * ld;
-        if (!g.norm[l]) {
-            for (int c = sub; c < W; c += 16) {
-                const float z = live ? Pl[(size_t)row * W + c] : 0.f;
-                const float dz = dr[c] * tw_act_grad(act, z);
-                dr[c] = dz;
-                if (Gl && live) Gl[(size_t)row * W + c] = dz;
-            }
-            __syncthreads();
-        } else {
-            const float* gamma = g.gamma[t][l];
-            const float* beta = g.beta[t][l];
-            float* xr = o + rr * ld;
-            const float rs = live ? g.rstd[t][(size_t)l * R + row] : 0.f;
-            float s1 = 0.f, s2 = 0.f;
-            for (int c = sub; c < W; c += 16) {
-                const float xh = live ? Pl[(size_t)row * W + c] : 0.f;
-                const float dy = dr[c] * tw_act_grad(act, xh * gamma[c] + beta[c]);
-                const float gg = dy * gamma[c];
-                s1 += gg;
-                s2 += gg * xh;
-                dr[c] = dy;
-                xr[c] = xh;
-            }
-            s1 = tw_sum16(s1) / (float)W;
-            s2 = tw_sum16(s2) / (float)W;
-            __syncthreads();
-            if (g.want_params) {                      // the tile's share of the shift / gain gradients: its 16 rows in order
-                float* Sb = g.Sb[t] + (size_t)tiles * p.off_col[l] + (size_t)blockIdx.x * W;
-                float* Sg = g.Sg[t] + (size_t)tiles * p.off_col[l] + (size_t)blockIdx.x * W;
-                for (int c = tid; c < W; c += 256) {
-                    float sb = 0.f, sg = 0.f;
-                    for (int r = 0; r < RO_ROWS; ++r) {
-                        const float dy = d[r * ld + c];
-                        sb += dy;
-                        sg += dy * o[r * ld + c];
-                    }
-                    Sb[c] = sb;
-                    Sg[c] = sg;
-                }
-            }
-            __syncthreads();
-            for (int c = sub; c < W; c += 16) {
-                const float dz = rs * (dr[c] * gamma[c] - s1 - xr[c] * s2);
-                dr[c] = dz;
-                if (Gl && live) Gl[(size_t)row * W + c] = dz;
-            }
-            __syncthreads();
-        }
-        if (l == 0) {
-            if (g.want_gx) {
-                float* gx = g.g_x[t];
-                ro_product<true>(d, ld, g.w[t][0], K, K, W, lane, wave, [&](int r, int n, float v) {
-                    if (row0 + r < R) gx[(size_t)(row0 + r) * K + n] = v;
-                });
-            }
-        } else {
-            ro_product<true>(d, ld, g.w[t][l], K, K, W, lane, wave, [&](int r, int n, float v) { o[r * ld + n] = v; });
-            __syncthreads();
-            cur ^= 1;
-        }
-    }
+    tw_backward_layers(g, t, g.K0, image(0), image(1), ld, tid, lane, wave, g.want_params != 0, g.want_gx != 0,
+                       TowerSaved{g, p, t, R, row0}, TowerGrads{g, p, t, R, row0, (long long)gridDim.x, (long long)blockIdx.x});
 }
 
 // out[c] += sum_r src[r][c] for every job: 64 columns x 64 rows per workgroup, the body of cdx_colsum_f32 (cdx_train.hip)

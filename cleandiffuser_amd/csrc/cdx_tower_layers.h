@@ -1,9 +1,13 @@
-// cdx_tower_layers.h -- the forward body of a Linear -> [LayerNorm] -> activation tower on one 16-row tile, once for the two kernels that
-// run it: cdx_tower_fwd_kernel (cdx_tower.hip: a training forward, which saves what the backward reads) and cdx_score_select_kernel
-// (cdx_select.hip: the critic in front of the candidate selection, which keeps the last layer's image only).  Per layer
-// z = h W^T + b (ro_product<false>); with a norm, 16 lanes per row take the mean and then the biased variance of the centred values over
-// the row in LDS (two passes, a fixed butterfly), xhat = (z - mean) rstd, y = xhat gamma + beta; h = act(y).  Host side (the end of the
-// file): the admission of the layers' sizes, shared by the entry points of both files.
+// cdx_tower_layers.h -- the forward and the backward-data body of a Linear -> [LayerNorm] -> activation tower on one 16-row tile, once
+// for the kernels that run them: cdx_tower_fwd_kernel / cdx_tower_bwd_kernel (cdx_tower.hip: a training forward, which saves what the
+// backward reads, and that backward), cdx_score_select_kernel (cdx_select.hip: the critic in front of the candidate selection, which keeps
+// the last layer's image only) and cdx_critic_step_kernel (cdx_critic_step.hip: target, forward, loss and backward-data of a critic step in
+// one launch, P_l and rstd_l staying in LDS).  Forward, per layer: z = h W^T + b (ro_product<false>); with a norm, 16 lanes per row take the
+// mean and then the biased variance of the centred values over the row in LDS (two passes, a fixed butterfly), xhat = (z - mean) rstd,
+// y = xhat gamma + beta; h = act(y).  Backward, per layer from the top: y from the saved P_l (xhat or z), dy = dH act'(y), with a norm
+// g = dy gamma, dz = rstd (g - mean(g) - xhat mean(g xhat)) and the tile's column sums of dy and dy xhat (rows in order), then
+// dH_{l-1} = dz W_l on the live weight (ro_product<true>).  Host side (the end of the file): the admission of the layers' sizes, shared by
+// the entry points of these files.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -21,6 +25,15 @@ __device__ __forceinline__ float tw_act(int act, float y) {
         case CDX_ACT_RELU: return cdx_act_relu(y);
         case CDX_ACT_TANH: return cdx_act_tanh(y);
         default: return y;
+    }
+}
+__device__ __forceinline__ float tw_act_grad(int act, float y) {
+    switch (act) {
+        case CDX_ACT_MISH: return cdx_act_mish_grad(y);
+        case CDX_ACT_SILU: return cdx_act_silu_grad(y);
+        case CDX_ACT_RELU: return cdx_act_relu_grad(y);
+        case CDX_ACT_TANH: return cdx_act_tanh_grad(y);
+        default: return 1.0f;
     }
 }
 // the sum over the 16 lanes of a row (tid >> 4): a butterfly, the same bits in every lane
@@ -89,6 +102,81 @@ __device__ __forceinline__ void tw_forward_layers(const G& g, int t, int K0, con
         }
         src = dst;
         ld_src = ld;
+    }
+}
+
+// The backward-data pass of tower `t` of request `g` (the per-layer fields of cdx_tower) on one tile: img[0] [16][ld] holds dH of the
+// last layer (zero in the rows past the batch and up to the next multiple of 16 past its width), img[1] is scratch.  What the forward
+// kept and where the results go is the caller's:
+//   saved.p(l, r, c)            P_l of tile row r (xhat of a normed layer, else z), 0 for a row past the batch;
+//   saved.rstd(l, r)            rstd_l of that row, 0 past the batch;
+//   sink.element(l, r, c, dz)   G_l, once per element (the sink drops rows past the batch);
+//   sink.sums(l, c, sb, sg)     the tile's sums of dy and dy xhat over its 16 rows in order, once per column of a normed layer;
+//   sink.gx(r, n, v)            g_x = dz_0 W_0, once per element.
+// `params`: call element / sums at all; `want_gx`: run the last product.  Called by all 256 threads behind a barrier that covers
+// img[0]; ends without one.
+template <class G, class Saved, class Sink>
+__device__ __forceinline__ void tw_backward_layers(const G& g, int t, int K0, float* img0, float* img1, int ld, int tid, int lane, int wave,
+                                                   bool params, bool want_gx, Saved saved, Sink sink) {
+    const int rr = tid >> 4, sub = tid & 15;
+    int cur = 0;
+    for (int l = g.n_layers - 1; l >= 0; --l) {
+        const int W = g.width[l], K = l ? g.width[l - 1] : K0, act = g.act[l];
+        float* d = cur ? img1 : img0;                 // dH_l, then dy, then dz: the A operand of the transposed product
+        float* o = cur ? img0 : img1;                 // xhat of a normed layer, then dH_{l-1}
+        float* dr = d + rr * ld;
+        if (!g.norm[l]) {
+            for (int c = sub; c < W; c += 16) {
+                const float z = saved.p(l, rr, c);
+                const float dz = dr[c] * tw_act_grad(act, z);
+                dr[c] = dz;
+                if (params) sink.element(l, rr, c, dz);
+            }
+            __syncthreads();
+        } else {
+            const float* gamma = g.gamma[t][l];
+            const float* beta = g.beta[t][l];
+            float* xr = o + rr * ld;
+            const float rs = saved.rstd(l, rr);
+            float s1 = 0.f, s2 = 0.f;
+            for (int c = sub; c < W; c += 16) {
+                const float xh = saved.p(l, rr, c);
+                const float dy = dr[c] * tw_act_grad(act, xh * gamma[c] + beta[c]);
+                const float gg = dy * gamma[c];
+                s1 += gg;
+                s2 += gg * xh;
+                dr[c] = dy;
+                xr[c] = xh;
+            }
+            s1 = tw_sum16(s1) / (float)W;
+            s2 = tw_sum16(s2) / (float)W;
+            __syncthreads();
+            if (params) {                             // the tile's share of the shift / gain gradients: its 16 rows in order
+                for (int c = tid; c < W; c += 256) {
+                    float sb = 0.f, sg = 0.f;
+                    for (int r = 0; r < RO_ROWS; ++r) {
+                        const float dy = d[r * ld + c];
+                        sb += dy;
+                        sg += dy * o[r * ld + c];
+                    }
+                    sink.sums(l, c, sb, sg);
+                }
+            }
+            __syncthreads();
+            for (int c = sub; c < W; c += 16) {
+                const float dz = rs * (dr[c] * gamma[c] - s1 - xr[c] * s2);
+                dr[c] = dz;
+                if (params) sink.element(l, rr, c, dz);
+            }
+            __syncthreads();
+        }
+        if (l == 0) {
+            if (want_gx) ro_product<true>(d, ld, g.w[t][0], K, K, W, lane, wave, [&](int r, int n, float v) { sink.gx(r, n, v); });
+        } else {
+            ro_product<true>(d, ld, g.w[t][l], K, K, W, lane, wave, [&](int r, int n, float v) { o[r * ld + n] = v; });
+            __syncthreads();
+            cur ^= 1;
+        }
     }
 }
 

@@ -11,7 +11,8 @@ LayerNorm/activation launch per layer); with autograd ON (the critics' training 
 together, is one forward and one backward row-tile launch (``engine/tower.py``: ``DQLCritic`` by default, ``TwinQ`` / ``V`` with
 ``CDX_TOWER=1`` -- the measurement of DESIGN.md 3m; ``CDX_TOWER=0`` or a tower it does not take: ``engine/train.py:chain_forward``, the
 library nodes the denoisers train on), IQL's two Adam optimisers and its Polyak target update on ``cdx_optim_f32``; on CPU the stock
-modules run.
+modules run.  A critic's whole training step -- target, TD expression, forward, loss, backward-data -- is one launch through
+``utils/critic_steps.py`` (``td_step`` / ``expectile_step``), which ``IQL.update_V`` / ``update_Q`` call.
 """
 from copy import deepcopy
 
@@ -197,24 +198,17 @@ class IQL(nn.Module):
         for p, p_targ in zip(self.Q.parameters(), self.Q_targ.parameters()):
             p_targ.data = mu * p_targ.data + (1 - mu) * p.data
 
+    # (the two steps are utils/critic_steps.py's calls: on a ROCm device one launch each for target, forward, loss and backward-data
+    # -- DESIGN.md 3p -- and the eager sequence on the CPU, with CDX_CRITIC_STEP=0 or on a refusal)
     def update_V(self, obs, act):
-        adv = self.Q_targ(obs, act) - self.V(obs)
-        loss = (torch.abs(self.iql_tau - (adv < 0).float()) * adv ** 2).mean()
-        self.optimV.zero_grad()
-        loss.backward()
-        self.optimV.step()
-        return loss.item()
+        from .critic_steps import expectile_step
+        return expectile_step(self.V, self.Q_targ, self.optimV, obs, act, tau=self.iql_tau)["loss"].item()
 
     def update_Q(self, obs, act, rew, obs_next, done):
-        with torch.no_grad():
-            target = rew + self.discount * (1 - done) * self.V(obs_next)
-        q1, q2 = self.Q.both(obs, act)
-        loss = ((q1 - target) ** 2 + (q2 - target) ** 2).mean()
-        self.optimQ.zero_grad()
-        loss.backward()
-        self.optimQ.step()
+        from .critic_steps import td_step
+        out = td_step(self.Q, self.V, self.optimQ, obs, act, rew, obs_next, done, discount=self.discount)
         self.update_target()
-        return loss.item()
+        return out["loss"].item()
 
     def save(self, path):
         torch.save(self.state_dict(), path)

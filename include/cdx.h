@@ -1038,6 +1038,76 @@ long long cdx_score_select_lds_bytes(const cdx_score_select* g);
 int cdx_score_select_f32(const cdx_score_select* g, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * A critic's TD or expectile training step in ONE launch (csrc/cdx_critic_step.hip).  Purely additive entries: no existing struct or
+ * call changes, so CDX_ABI_VERSION stays 19.  Reference: the critic steps of pipelines/dql_d4rl_mujoco.py:80-94,
+ * dql_d4rl_antmaze.py:79-98, idql_d4rl_mujoco.py:84-107 (utils/iql.py:62-84), qgpo_d4rl_mujoco.py:141-152: a frozen target evaluated
+ * without a gradient, y = rew + discount (1 - done) T, an MSE or expectile loss of one or two live towers against y, its backward.
+ * One workgroup of 4 wave64 owns 16 live rows of one live tower: grid (ceil(R / 16), live.n_towers).  Four phases:
+ *   target    target.n_towers (1 or 2) frozen towers of one shape over the rows [z0 | z1]: z0 (R, B0) one row per live row, z1
+ *             (R K, B1) K rows per live row (row r K + j is candidate j of live row r; NULL with B1 == 0); target.K0 == B0 + B1.  K passes,
+ *             per pass every tower's forward on the tile, then per live row
+ *               CDX_CRITIC_MIN      (K == 1) T = min over the towers;
+ *               CDX_CRITIC_MAX      T = min over the towers of the max over the K rows;
+ *               CDX_CRITIC_SOFTMAX  q_j = min over the towers, T = sum_j w_j q_j / sum_j w_j, w_j = exp(beta q_j - max_i beta q_i)
+ *             (a NaN stays).  y = rew + discount (1 - done) T, or y = T with rew == NULL.  Both live towers of a tile compute the same y
+ *             in the same order; tower 0 writes y_out (R) and y_part[tile] = (the sum of y over the tile's rows in order) / R.
+ *   forward   live tower t on [x0 | x1] (x0 (R, A0), x1 (R, A1) or NULL with A1 == 0; live.K0 == A0 + A1), as cdx_tower_fwd_f32.  Tower 0
+ *             writes the concatenated input x_cat (R, live.K0); every tower its H_l (layer-major as cdx_tower's, layers 0 .. n_layers - 2)
+ *             and q_out[t] (R).  P_l and rstd_l stay in LDS.
+ *   loss      CDX_CRITIC_MSE        e = q - y, l = e^2, dq = 2 e / R;
+ *             CDX_CRITIC_EXPECTILE  a = y - q, w = |tau - 1[a < 0]|, l = w a^2, dq = -2 w a / R.
+ *             loss_part[t][tile] = (the sum of l over the tile's rows in order) / R: the sum over tiles and towers is the step's loss.
+ *   backward  from dq, as cdx_tower_bwd_f32 with want_params and without g_x: G_l, Sb, Sg in cdx_tower's layout.
+ * The weight / bias gradients are the caller's: one cdx_conv_wgrad_batch_f32 with jobs (G_l, H_{l-1} or x_cat, R); the gain / shift
+ * gradients, the loss and the mean of y one cdx_colsum_batch_f32 over Sg / Sb / loss_part / y_part.  Caller-owned memory, one kernel per
+ * call enqueued on `hip_stream`, no synchronisation, no allocation; no atomics, one fixed lane and order per element: bit-reproducible.
+ * Limits (CDX_EINVAL with a message, before anything is launched): both nets within the limits of cdx_tower and their last width 1;
+ * 1 <= K <= CDX_CRITIC_MAX_K (K == 1 in CDX_CRITIC_MIN); R K <= 2^31 - 17; done required with rew; the LDS plan
+ * (cdx_critic_step_lds_bytes: two activation images, P_l and rstd_l of the live tower, the K target values) at most 160 KiB.  R == 0 is
+ * CDX_OK.
+ * ---------------------------------------------------------------------------------------------- */
+#define CDX_CRITIC_MIN 0
+#define CDX_CRITIC_MAX 1
+#define CDX_CRITIC_SOFTMAX 2
+#define CDX_CRITIC_MSE 0
+#define CDX_CRITIC_EXPECTILE 1
+#define CDX_CRITIC_MAX_K 16
+typedef struct cdx_critic_net {
+    int32_t K0, n_towers, n_layers, reserved;
+    int32_t width[CDX_TOWER_MAX_LAYERS];
+    int32_t norm[CDX_TOWER_MAX_LAYERS];
+    int32_t act[CDX_TOWER_MAX_LAYERS];
+    float eps[CDX_TOWER_MAX_LAYERS];
+    const float* w[2][CDX_TOWER_MAX_LAYERS];            /* as cdx_tower */
+    const float* b[2][CDX_TOWER_MAX_LAYERS];
+    const float* gamma[2][CDX_TOWER_MAX_LAYERS];
+    const float* beta[2][CDX_TOWER_MAX_LAYERS];
+} cdx_critic_net;
+typedef struct cdx_critic_step {
+    int32_t R, K;                                       /* live rows; target rows per live row */
+    int32_t A0, A1, B0, B1;                             /* widths of x0, x1, z0, z1 */
+    int32_t reduce, loss;                               /* CDX_CRITIC_MIN / MAX / SOFTMAX; CDX_CRITIC_MSE / EXPECTILE */
+    float discount, beta, tau;                          /* beta: CDX_CRITIC_SOFTMAX; tau: CDX_CRITIC_EXPECTILE */
+    int32_t reserved;
+    cdx_critic_net live, target;
+    const float *x0, *x1;                               /* (R, A0); (R, A1) or NULL */
+    const float *z0, *z1;                               /* (R, B0); (R K, B1) or NULL */
+    const float *rew, *done;                            /* (R) each, or both NULL: y = T */
+    float* y_out;                                       /* (R) */
+    float* y_part;                                      /* (ceil(R / 16)) */
+    float* q_out[2];                                    /* (R) */
+    float* loss_part[2];                                /* (ceil(R / 16)) */
+    float* x_cat;                                       /* (R, live.K0) */
+    float* H[2];                                        /* as cdx_tower */
+    float* G[2];
+    float* Sb[2];
+    float* Sg[2];
+} cdx_critic_step;
+/* bytes of LDS one workgroup of this request needs, or a negative CDX_E* code when the sizes are out of range */
+long long cdx_critic_step_lds_bytes(const cdx_critic_step* g);
+int cdx_critic_step_f32(const cdx_critic_step* g, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Decision Veteran's horizon critic in ONE call (csrc/cdx_hcritic.hip).  Purely additive entries: no existing struct or call
  * changes, so CDX_ABI_VERSION stays 19.  Reference: utils/building_blocks.py:149-229 (DVTransformerBlock / DVHorizonCritic), scored on
  * num_envs x planner_num_candidates freshly sampled plans at every environment step of pipelines/veteran_d4rl_{kitchen,antmaze,maze2d}.py.
