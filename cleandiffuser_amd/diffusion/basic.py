@@ -73,13 +73,14 @@ class DiffusionModel:
         """``loss = self.loss(...); loss.backward()`` of every ``update()`` (reference diffusionsde.py:125-131, ddpm.py:98-104,
         newedm.py:178-184).  On a ROCm device, for the denoisers the native training path serves, the pair is ONE HIP-graph replay once
         the first step passed the capturability probe (engine/train.py:GraphedStep; CDX_TRAIN_GRAPH=0 keeps the eager pair)."""
-        from ..engine import train
-        g = train.graphed_step(self, x0, condition, kwargs)
-        if g is None:
-            loss = self.loss(x0, condition, **kwargs)
-            with train.grads_in_place(self.model.parameters()):               # the library's nodes add parameter gradients straight into .grad
-                loss.backward()
-            return loss
+        from ..engine import denoise, train
+        with denoise.inside_update():                                         # (update() keeps its own route: loss() does not take the fused node here)
+            g = train.graphed_step(self, x0, condition, kwargs)
+            if g is None:
+                loss = self.loss(x0, condition, **kwargs)
+                with train.grads_in_place(self.model.parameters()):           # the library's nodes add parameter gradients straight into .grad
+                    loss.backward()
+                return loss
         loss = g.replay(x0, condition)
         if hasattr(self.optimizer, "_gver"):
             # a replay writes gradients without moving their version counters: the ones the captured step writes ARE written (and only

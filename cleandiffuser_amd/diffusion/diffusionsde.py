@@ -121,8 +121,17 @@ class BaseDiffusionSDE(DiffusionModel):
         raise NotImplementedError
 
     def loss(self, x0, condition=None, **kwargs):
+        # the row-MLP denoisers outside update(): noise add, net, weighted square and mean in one forward and one backward launch
+        # (engine/denoise.py; the same draws in the same order, so a seeded call does not depend on the route)
+        from ..engine import denoise
+        fused = denoise.try_loss(self, x0, condition, kwargs)
+        if fused is not None:
+            return fused
         xt, t, eps = self.add_noise(x0)
         cond = self.model["condition"](condition) if condition is not None else None
+        return self._loss_of(x0, xt, t, eps, cond, kwargs)
+
+    def _loss_of(self, x0, xt, t, eps, cond, kwargs):
         target = eps if self.predict_noise else x0
         err = (self.model["diffusion"](xt, t, cond) - target) ** 2
         err = err * self.loss_weight * (1 - self.fix_mask)
@@ -344,10 +353,19 @@ class DiscreteDiffusionSDE(BaseDiffusionSDE):
         # wait for whatever the stream is still running, e.g. the previous sample() call)
         self._alpha_host, self._sigma_host = self.alpha.detach().float().cpu(), self.sigma.detach().float().cpu()
 
-    def add_noise(self, x0, t=None, eps=None):
+    def _noise_draws(self, x0, t=None, eps=None):
+        """(t, eps) of ``add_noise``: its draws, in its order."""
         t = torch.randint(self.diffusion_steps, (x0.shape[0],), device=self.device) if t is None else t
         eps = torch.randn_like(x0) if eps is None else eps
-        alpha, sigma = at_least_ndim(self.alpha[t], x0.dim()), at_least_ndim(self.sigma[t], x0.dim())
+        return t, eps
+
+    def _alpha_sigma_rows(self, t):
+        return self.alpha[t], self.sigma[t]
+
+    def add_noise(self, x0, t=None, eps=None):
+        t, eps = self._noise_draws(x0, t, eps)
+        alpha, sigma = self._alpha_sigma_rows(t)
+        alpha, sigma = at_least_ndim(alpha, x0.dim()), at_least_ndim(sigma, x0.dim())
         xt = alpha * x0 + sigma * eps
         return (1. - self.fix_mask) * xt + self.fix_mask * x0, t, eps
 
@@ -412,10 +430,18 @@ class ContinuousDiffusionSDE(BaseDiffusionSDE):
     def _alpha_sigma(self, t):
         return self.noise_schedule_funcs["forward"](t, **(self.noise_schedule_params or {}))
 
-    def add_noise(self, x0, t=None, eps=None):
+    def _noise_draws(self, x0, t=None, eps=None):
+        """(t, eps) of ``add_noise``: its draws, in its order."""
         lo, hi = self.t_diffusion
         t = (torch.rand((x0.shape[0],), device=self.device) * (hi - lo) + lo) if t is None else t
         eps = torch.randn_like(x0) if eps is None else eps
+        return t, eps
+
+    def _alpha_sigma_rows(self, t):
+        return self._alpha_sigma(t)
+
+    def add_noise(self, x0, t=None, eps=None):
+        t, eps = self._noise_draws(x0, t, eps)
         alpha, sigma = self._alpha_sigma(t)
         alpha, sigma = at_least_ndim(alpha, x0.dim()), at_least_ndim(sigma, x0.dim())
         xt = alpha * x0 + sigma * eps

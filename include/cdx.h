@@ -1108,6 +1108,62 @@ long long cdx_critic_step_lds_bytes(const cdx_critic_step* g);
 int cdx_critic_step_f32(const cdx_critic_step* g, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The denoising loss of the row-MLP denoisers in one forward and one backward launch (csrc/cdx_denoise.hip).  Purely additive entries:
+ * no existing struct or call changes, so CDX_ABI_VERSION stays 19.  Reference: ``bc_loss = actor.loss(act, obs)`` of
+ * pipelines/dql_d4rl_*.py and edp_d4rl_mujoco.py:97 (diffusion/diffusionsde.py:94-110 over nn_diffusion/dqlmlp.py:30-52 /
+ * dvinvmlp.py:30-47) and EDP's action approximation ``actor.model["diffusion"](noisy_act, t, cond)`` (edp_d4rl_mujoco.py:100-108).
+ * One workgroup of 4 wave64 owns 16 rows.  Forward, per tile:
+ *   noise add  xt = (1 - m) (a_r x0 + s_r eps) + m x0 with the caller's rows a = alpha[t], s = sigma[t] (R) and the fix mask m (A) or
+ *              NULL; skipped when `xt` is given (given-input mode).
+ *   time MLP   temb = Linear(Mish(Linear(emb0))), emb0 (R, E) = map_noise(t) from the caller; saves Zt, Ht (R, 2E).
+ *   features   feat (R, A+E+O) = [xt | temb | cond]; cond NULL reads as zeros.
+ *   trunk      3 x (Linear(., W) -> Mish), saving Z, H as (3, R, W) layer-major; head: pred (R, A).
+ *   loss       (loss_mode) l = (pred - target)^2 lw[e] (1 - m[e]) wr[row], target = eps (predict_noise) or x0; lw (A) and wr (R)
+ *              optional; loss_part[tile] = (the sum of l over the tile in row-major order) / (R A): the sum over the tiles is the loss.
+ * Backward, per tile: d loss / d pred = g_loss[0] 2 (pred - target) lw (1 - m) wr / (R A) (loss_mode; g_loss a device scalar) or the
+ * caller's rows g_pred (R, A); then the head, the trunk and the time MLP transposed.  Writes G_head (R, A), G_l over Z_l, G_t2 (R, E) =
+ * d loss / d temb, Gt over Zt and, each only when its pointer is given, g_xt (R, A), g_cond (R, O; needs cond) and g_emb0 (R, E).
+ * The weight / bias gradients are the caller's: one cdx_conv_wgrad_f32 product (taps 1) per layer over the R rows with (p, q) =
+ * (Gt, emb0), (G_t2, Ht), (G_0, feat), (G_1, H_0), (G_2, H_1), (G_head, H_2).  Caller-owned memory and stream, one kernel per call, no
+ * allocation, no synchronisation; no atomics, one fixed lane and order per element: bit-reproducible.
+ * Limits (CDX_EINVAL with a message, before anything is launched): W % 16 == 0, W <= 512, A + E + O <= 512, A <= 64, 2 E <= 512; the
+ * LDS plan (cdx_denoise_lds_bytes: two activation images and one (16 x A) tile) at most 160 KiB.  R == 0 is CDX_OK.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct cdx_denoise {
+    int32_t R, A, E, O, W;
+    int32_t predict_noise;     /* the loss target is eps (1) or x0 (0) */
+    int32_t loss_mode;         /* 1: the loss and its gradient; 0: prediction mode (pred out, g_pred in) */
+    int32_t reserved;
+    const float *tw1, *tb1;    /* time_mlp.0: (2E, E), (2E) */
+    const float *tw2, *tb2;    /* time_mlp.2: (E, 2E), (E) */
+    const float *w1, *b1;      /* (W, A+E+O), (W) */
+    const float *w2, *b2;      /* (W, W), (W) */
+    const float *w3, *b3;      /* (W, W), (W) */
+    const float *wh, *bh;      /* (A, W), (A) */
+    const float* xt;           /* (R, A) given-input mode, or NULL: the noise add runs on x0 / eps / a / s */
+    const float *x0, *eps;     /* (R, A) each */
+    const float *a, *s;        /* (R) each */
+    const float* emb0;         /* (R, E) */
+    const float* cond;         /* (R, O) or NULL */
+    const float* fix_mask;     /* (A) or NULL */
+    const float* lw;           /* (A) or NULL: the loss weight */
+    const float* wr;           /* (R) or NULL: the weighted-regression rows */
+    float *Zt, *Ht;            /* saved by forward: (R, 2E) each */
+    float* feat;               /* (R, A+E+O) */
+    float *Z, *H;              /* (3, R, W) each */
+    float* pred;               /* (R, A) */
+    float* loss_part;          /* (ceil(R / 16)), loss_mode */
+    const float* g_loss;       /* backward, loss_mode: device scalar d L / d loss */
+    const float* g_pred;       /* backward, prediction mode: (R, A) */
+    float *G_head, *G_t2;      /* written by backward: (R, A), (R, E) */
+    float *g_xt, *g_cond, *g_emb0;   /* optional outputs of backward */
+} cdx_denoise;
+/* bytes of LDS one workgroup of this request needs (either kernel), or a negative CDX_E* code for a null request or a size < 1 */
+long long cdx_denoise_lds_bytes(const cdx_denoise* g);
+int cdx_denoise_fwd_f32(const cdx_denoise* r, void* hip_stream);
+int cdx_denoise_bwd_f32(const cdx_denoise* r, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Decision Veteran's horizon critic in ONE call (csrc/cdx_hcritic.hip).  Purely additive entries: no existing struct or call
  * changes, so CDX_ABI_VERSION stays 19.  Reference: utils/building_blocks.py:149-229 (DVTransformerBlock / DVHorizonCritic), scored on
  * num_envs x planner_num_candidates freshly sampled plans at every environment step of pipelines/veteran_d4rl_{kitchen,antmaze,maze2d}.py.
