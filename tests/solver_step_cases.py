@@ -223,10 +223,10 @@ def case_of(name, executor="mlp"):
     return SimpleNamespace(**{**vars(case), "x_shape": spec.x_shape, "w_cfg": w})
 
 
-def build(name, executor="mlp", device="cpu", dtype=torch.float32, case=None):
-    """The agent of a case on this package's classes, eval mode."""
+def build(name, executor="mlp", device="cpu", dtype=torch.float32, case=None, spec=None):
+    """The agent of a case on this package's classes, eval mode.  `spec`: a net outside ``EXECUTORS`` (tests/executor_shape_cases.py)."""
     from cleandiffuser_amd.utils import load_synth
-    case, spec, lib = case or case_of(name, executor), EXECUTORS[executor], _cases.lib_namespace("amd")
+    case, spec, lib = case or case_of(name, executor), spec or EXECUTORS[executor], _cases.lib_namespace("amd")
     net = load_synth(getattr(lib, spec.net[0])(**spec.net[1]), 81)
     head = [m for m in net.modules() if isinstance(m, (torch.nn.Linear, torch.nn.Conv1d))][-1]      # the output layer, scaled
     with torch.no_grad():
@@ -320,13 +320,13 @@ def spied(net, seen):
             setattr(dispatch, n, orig[n])
 
 
-def host_run(name, dtype, executor="mlp", inp=None, case=None):
+def host_run(name, dtype, executor="mlp", inp=None, case=None, spec=None):
     """One CPU run of case `name` on the package's host loop in `dtype` -> x, the plan, the signatures of its step records, the clamp
     shares (per step; then the clip of the finished sample where the class has one) and the classifier-free halves."""
     from cleandiffuser_amd.engine.runtime import _predicts_noise
     case = case or case_of(name, executor)
     inp = make_inputs(name, executor) if inp is None else inp
-    agent = build(name, executor, "cpu", dtype, case)
+    agent = build(name, executor, "cpu", dtype, case, spec)
     seen = SimpleNamespace(plan=None, xt=None, cfg2=False, cond=None, w_cfg=0.0, share=[], halves=[], shape=inp["prior"].shape)
     with spied(agent.model_ema["diffusion"], seen):
         x = sample(agent, case, inp, dtype=dtype)
