@@ -40,6 +40,19 @@ CASES = {
     # the shipped widths at a small batch; no EMA update (gradients too large for the fixture: not stored)
     "shipped_b8": _c(8, 16, 17, 6, 64, [256, 256, 256], update_ema=False, grads=False),
 }
+GOLDEN_TABLE = list(CASES)         # the cases tests/golden/qgpo_cep.npz holds a record of
+
+# the edges of what cep_plan / em_plan admit (A <= 64, O <= 512, Ec <= 128, widths <= 512, LDS <= 160 KiB): no record of the real
+# reference, held to float64 autograd of the package's own loss on the CPU and to the float64 restatement on the device
+ENVELOPE = {
+    # the kitchen classifier (obs 60, act 9) at the shipped widths: 85 KiB of LDS
+    "kitchen_k16_b3": _c(3, 16, 60, 9, 64, [256, 256, 256]),
+    # every limit at once: O = 512 (32 K blocks in obs_proj), A = 64, Ec = 128, two 512-wide layers (both sweeps): 133 KiB of LDS
+    "limits_k8_b3": _c(3, 8, 512, 64, 128, [512, 512], head_scale=4.0),
+    # a partial second sweep (272 = 17 column tiles), O = 85 (six K blocks through the scalar weight loads), A = 17
+    "sweep272_k4_b5": _c(5, 4, 85, 17, 32, [272, 272]),
+}
+CASES.update(ENVELOPE)
 TABLE = list(CASES)
 
 

@@ -44,6 +44,19 @@ CASES = {
     "unequal_r33": _c(33, 17, 6, [32, 48, 16, 1], ["silu", "relu", "mish", None], 2, 17, 6, [48, 32, 1], _IQL, 2),
     "wide512_r17": _c(17, 11, 3, [512, 1], ["tanh", None], 2, 11, 3, [32, 32, 1], _IQL, 2),
 }
+# the edges of what critic_plan admits (K0 <= 512, widths <= 512, K <= 16, LDS <= 160 KiB)
+_W512 = ["tanh", None]
+ENVELOPE = {
+    # the kitchen DQLCritic (obs 60 + act 9), live and target: five K blocks with a ragged end, scalar weight loads, 83 KiB of LDS
+    "kitchen_r17_k69": _c(17, 60, 9, [256, 256, 256, 1], _DQL, 2, 60, 9, [256, 256, 256, 1], _DQL, 2),
+    # the widest input and the widest layer, A1 = 64: 32 K blocks, both sweeps of the product, 98 KiB of LDS
+    "widest_r17_k512": _c(17, 448, 64, [512, 1], _W512, 2, 448, 64, [512, 1], _W512, 2),
+    # the grouped target at the kitchen sizes
+    "kitchen_antmaze_k10_r17": _c(17, 60, 9, [256, 256, 256, 1], _DQL, 2, 60, 9, [256, 256, 256, 1], _DQL, 2, group=10, reduce="max"),
+    # a partial second sweep (272 = 17 column tiles) over K0 = 85, a single live tower on a V-like target
+    "sweep272_r33_k85": _c(33, 76, 9, [272, 272, 1], _IQL, 1, 76, 0, [272, 1], ["mish", None], 1),
+}
+CASES.update(ENVELOPE)
 TABLE = list(CASES)
 ALL_ZERO_GRADS: dict = {}          # case -> names of gradients that are identically zero by construction (none in this table)
 
@@ -273,3 +286,12 @@ def run_dql_calls(U, case, device="cpu", adam=torch.optim.Adam) -> dict:
     out["dql/loss"] = np.array(losses, dtype=np.float64)
     out["dql/sums"] = cs.checksums(critic)
     return out
+
+
+def sizes_request(critic_step, live, target, K=1):
+    """A ``CdxCriticStep`` of sizes alone (every pointer null) for `live` / `target` = (K0, widths): what the C side's size checks and
+    LDS plan read."""
+    import ctypes
+    mk = lambda k0, widths: critic_step.CdxCriticNet(K0=k0, n_towers=2, n_layers=len(widths), width=(ctypes.c_int32 * 6)(*widths),   # noqa: E731
+                                                     act=(ctypes.c_int32 * 6)(), norm=(ctypes.c_int32 * 6)())
+    return critic_step.CdxCriticStep(R=40, K=K, A0=live[0], A1=0, B0=target[0] - 1, B1=1, reduce=1, loss=0, live=mk(*live), target=mk(*target))

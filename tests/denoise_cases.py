@@ -36,8 +36,25 @@ CASES = {
     "dv64_r33_pred_nocondgrad": _c(DV64, 33, "pred", cond_grad=False, seed=78),
     "dql_r16_pred_nocond": _c(DQL, 16, "pred", cond=False, seed=79),
 }
+LOSS_CASES = [n for n, c in CASES.items() if c.mode == "loss"]          # (the cases tests/golden/denoise_steps.npz holds a record of)
+
+# the edges of what dn_check admits (A <= 64, 2 E <= 512, A + E + O <= 512, W <= 512), on the nets of rollout_cases.ENVELOPE and one at E = 256
+DV512, DV272, DV48A33, KITCHEN = ("DVInvMlp", 160, 64, 128, 512), ("DVInvMlp", 60, 17, 16, 272), ("DVInvMlp", 5, 33, 16, 48), ("DQLMlp", 60, 9, 16, None)
+ENVELOPE = {
+    # every limit at once (F = 512, W = 512: 68 KiB of LDS), with everything the loss can carry
+    "limits_r17_a64_f512_w512_eps_mask_lw_wr": _c(DV512, 17, "loss", predict_noise=True, mask=True, lw=True, wr=True, seed=91),
+    # a partial second sweep (272 = 17 column tiles), A = 17, F = 153: ten K blocks through the scalar weight loads
+    "dv272_r33_a17_x0": _c(DV272, 33, "loss", seed=92),
+    # A = 33: three trips of the element loops, a ragged third head tile, with a gradient for the condition and for xt
+    "dv48_r17_a33_pred": _c(DV48A33, 17, "pred", seed=93),
+    # the kitchen policy (obs 60, act 9): F = 85, W = 256
+    "kitchen_dql_r33_eps_lw": _c(KITCHEN, 33, "loss", predict_noise=True, lw=True, seed=94),
+    "kitchen_dql_r17_pred": _c(KITCHEN, 17, "pred", seed=95),
+    # the widest time MLP: 2 E = 512 (its hidden layer is an MFMA A operand of two sweeps), F = 267
+    "dv32_r17_e256_x0_mask": _c(("DVInvMlp", 4, 3, 256, 32), 17, "loss", mask=True, seed=96),
+}
+CASES.update(ENVELOPE)
 TABLE = list(CASES)
-LOSS_CASES = [n for n, c in CASES.items() if c.mode == "loss"]
 PARAMS = [f"{m}.{leaf}" for m in ("time_mlp.0", "time_mlp.2", "mid_layer.0", "mid_layer.2", "mid_layer.4", "final_layer") for leaf in ("weight", "bias")]
 
 

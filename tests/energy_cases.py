@@ -56,6 +56,22 @@ CASES = {
     # the shipped widths: the full-size LDS plan
     "shipped_b50": _c(base=SHIPPED),
 }
+GOLDEN_TABLE = list(CASES)         # the cases tests/golden/qgpo_guided.npz holds a record of
+
+# the edges of what en_plan / em_plan admit (A <= 64, O <= 512, E, Ec <= 128, widths <= 512, a concat input <= 1024, LDS <= 160 KiB): no
+# record of the real reference, held to the float64 host loop on the CPU and to the float64 restatement on the device
+ENVELOPE = {
+    # the kitchen pipeline (obs 60, act 9) at the shipped widths
+    "kitchen_b17": _c(base=SHIPPED, O=60, A=9, S=3, B=17),
+    # A = 33 under a mask: three trips of the element loops, three column tiles in the out layer and in act_proj's transpose
+    "a33_b17_mask": _c(A=33, S=3, B=17, mask=True),
+    # a concat input of 272 + 272 = 544 columns, a partial second sweep (272 = 17 column tiles), and O = 85: six K blocks with a ragged
+    # end through the scalar weight loads of obs_proj
+    "concat544_b33_o85": _c(hidden=[32, 272, 272], O=85, S=2, B=33),
+    # the limits that fit 160 KiB together: A = 64, O = 512, E = Ec = 128, a 512-wide block in either net (139 KiB)
+    "limits_b17": _c(A=64, O=512, emb=128, hidden=[512, 128], clf_emb=128, clf_hidden=[512], clf_time="untrainable_fourier", S=2, B=17),
+}
+CASES.update(ENVELOPE)
 TABLE = list(CASES)
 DISCRETE_STEPS = 20
 

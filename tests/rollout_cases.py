@@ -54,6 +54,21 @@ SHAPES = {
 }
 CASES.update(SHAPES)
 
+# the edges of what ro_check admits (A <= 64, A + E + O <= 512, W <= 512): more than one trip of the (16 x A) element loops, more than
+# one column tile in the head, both sweeps of the product, many K blocks with a ragged end.  Held to float64 on the CPU too (TABLE).
+ENVELOPE = {
+    # every limit at once: A = 64, E = 128, O = 320 (F = 512), W = 512
+    "limits_b17_a64_f512_w512_s2": _c(("DVInvMlp", 160, 64, 128, 512), 81, 17, 2, "ddpm", True, 1.0),
+    # a partial second sweep (272 = 17 column tiles), A = 17 (two head tiles), F = 153: ten K blocks through the scalar weight loads
+    "b33_a17_w272_s3_ddim": _c(("DVInvMlp", 60, 17, 16, 272), 82, 33, 3, "ddim", True, 2.5),
+    # A = 33 under a mask: three trips of the element loops, a ragged third head tile, three K blocks in the transposed head product
+    "b17_a33_w48_s3_x0": _c(("DVInvMlp", 5, 33, 16, 48), 84, 17, 3, "ddpm", False, 0.25),
+    # the kitchen policy (obs 60, act 9): F = 85, W = 256
+    "kitchen_dql_b17_s3": _c(("DQLMlp", 60, 9, 16, None), 85, 17, 3, "ddpm", True, 1.0),
+}
+CASES.update(ENVELOPE)
+TABLE += list(ENVELOPE)
+
 
 def build(case, lib, device="cpu", dtype=torch.float32):
     """(agent, inputs) of a case on `device`: synthetic weights, IdentityCondition, randn observations, recorded noise."""

@@ -1,5 +1,6 @@
 """The cases the candidate-selection tests share (engine/select.py, utils/selection.py, csrc/cdx_select.hip): the shipped critics at hidden
-width 32 or 48, so a case takes milliseconds.  Every case builds its critic and inputs from its seed; the seeds were chosen on the CPU
+width 32 or 48, so a case takes milliseconds, and the ENVELOPE group at the edges of the sizes the kernels admit (up to K0 = 512, a
+512-wide layer and K = 1024 candidates; still one to 128 tiles).  Every case builds its critic and inputs from its seed; the seeds were chosen on the CPU
 (``decision_margin`` / ``sample_margin`` below) so that every decision of every state keeps the margin its test asserts."""
 from types import SimpleNamespace
 
@@ -24,6 +25,16 @@ CASES = {
     "mlp_noobs_s2_k40": _c(2, 40, 0, 6, "mlp", 32, 0),           # no observation block
     "twinq_s2_k33_k021": _c(2, 33, 17, 4, "twinq", 32, 0),       # O + A = 21: scalar weight loads, zero padding of the image
 }
+# the edges of what score_plan / select_check admit (A <= 64, O + A <= 512, widths <= 512, K <= 1024, top_k <= 16, LDS <= 160 KiB); `hidden`
+# as a list: the hidden widths of the Mlp
+ENVELOPE = {
+    "kitchen_dql_s2_k50": _c(2, 50, 60, 9, "dql", 256, 0),              # the kitchen DQLCritic: K0 = 69, five K blocks, scalar weight loads
+    "twinq_s2_k17_o448_a64": _c(2, 17, 448, 64, "twinq", 32, 0),        # O + A = 512, A = 64: the widest image, 32 K blocks
+    "mlp_s2_k1024": _c(2, 1024, 17, 6, "mlp", 48, 8),                   # 64 tiles per state; all 16 `taken` bits of a lane in the reduction
+    "mlp_s2_k17_k0512_w512": _c(2, 17, 448, 64, "mlp", [512], 0),       # the widest critic: K0 = 512 into one 512-wide layer, 96 KiB of LDS
+    "dql_s2_k16_w272_k085": _c(2, 16, 76, 9, "dql", 272, 0),            # a partial second sweep (272 = 17 column tiles) on the one-launch path
+}
+CASES.update(ENVELOPE)
 TABLE = list(CASES)
 
 
@@ -37,7 +48,7 @@ def build_critic(case, dtype=torch.float32, device="cpu"):
     elif case.kind == "twinq":
         m = TwinQ(case.O, case.A, hidden_dim=case.hidden)
     else:
-        m = Mlp(case.O + case.A, [case.hidden, case.hidden], 1, nn.SiLU())
+        m = Mlp(case.O + case.A, case.hidden if isinstance(case.hidden, list) else [case.hidden, case.hidden], 1, nn.SiLU())
     g = torch.Generator().manual_seed(1000 + case.seed)
     with torch.no_grad():
         for mod in m.modules():
@@ -137,3 +148,12 @@ def tie_case():
     scores = torch.randint(0, 4, (S * K,), generator=g).float() / 2
     wide = torch.randn(S * K, 9, generator=g)
     return SimpleNamespace(S=S, K=K, top_k=4, scores=scores, wide=wide, cols=slice(2, 7))
+
+
+def c_request(E, O=7, A=3, widths=(16, 1), S=4, K=5, **sel):
+    """A ``CdxScoreSelect`` of sizes alone (every pointer null unless `sel` gives one): what the C side's size checks and LDS plan read."""
+    g = E.CdxScoreSelect(O=O, A=A, n_towers=1, n_layers=len(widths))
+    g.sel = E.CdxSelect(S=S, K=K, temperature=1.0, **sel)
+    for l, w in enumerate(widths[:E.tower.MAX_LAYERS]):
+        g.width[l], g.eps[l] = w, 1e-5
+    return g

@@ -78,7 +78,7 @@ def test_reference_step_equals_float64_autograd(name, amd_lib):
         assert max(float(g.abs().max()) for g in out.grads) > 1e-3
 
 
-@pytest.mark.parametrize("name", cc.TABLE)
+@pytest.mark.parametrize("name", cc.GOLDEN_TABLE)
 def test_reference_step_matches_the_fixture(name, amd_lib):
     """``reference_step`` in float32 on the CPU against the first ``update()`` of the real reference (tests/golden/qgpo_cep.npz): the
     scalars at rtol = atol = 1e-4, every recorded gradient at 2e-4 x max |g_ref|."""
@@ -136,7 +136,7 @@ def _untouched(clf, before):
                for p, (p0, g0) in zip(clf.model.parameters(), before))
 
 
-@pytest.mark.parametrize("name", cc.TABLE)
+@pytest.mark.parametrize("name", cc.GOLDEN_TABLE)
 def test_three_updates_on_the_fused_route_reproduce_the_fixture(name, routed, amd_lib):
     """The accepted cases are taken, and with the native call replaced by ``reference_step`` three ``update()`` calls reproduce the real
     reference: each returned dict and, after the third call, the checksums of every parameter and every EMA parameter at rtol = atol =

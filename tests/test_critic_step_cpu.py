@@ -76,10 +76,7 @@ def test_the_restatement_is_the_inline_step_in_float64(name, refs):
             assert cc.rel_err(a, b) <= 1e-10, (name, t, i, cc.rel_err(a, b))
 
 
-def _sizes_request(critic_step, live, target, K=1):
-    mk = lambda k0, widths: critic_step.CdxCriticNet(K0=k0, n_towers=2, n_layers=len(widths), width=(ctypes.c_int32 * 6)(*widths),   # noqa: E731
-                                                     act=(ctypes.c_int32 * 6)(), norm=(ctypes.c_int32 * 6)())
-    return critic_step.CdxCriticStep(R=40, K=K, A0=live[0], A1=0, B0=target[0] - 1, B1=1, reduce=1, loss=0, live=mk(*live), target=mk(*target))
+_sizes_request = cc.sizes_request
 
 
 def test_the_lds_plan_is_the_librarys():

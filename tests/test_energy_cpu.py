@@ -44,7 +44,7 @@ def test_reference_restatement_equals_the_host_loop(name):
     _close(q.logp_out, ref.log_p, "log_p")
 
 
-@pytest.mark.parametrize("name", ec.TABLE)
+@pytest.mark.parametrize("name", ec.GOLDEN_TABLE)
 def test_reference_restatement_matches_the_fixture(name):
     """``reference_run`` in float32 on the CPU against what the real reference returned (tests/golden/qgpo_guided.npz) at the project's
     rtol = atol = 1e-4; the request is the one of the float64 run (plan, x_T) in float32."""

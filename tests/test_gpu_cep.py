@@ -63,7 +63,7 @@ def test_the_kernel_matches_the_float64_restatement(name, amd_lib):
         assert all(float(g[k].abs().max()) == 0.0 for k in g if k.startswith("G")) and float(got.stats[:, 0].abs().max()) == 0.0
 
 
-@pytest.mark.parametrize("name", cc.TABLE)
+@pytest.mark.parametrize("name", cc.GOLDEN_TABLE)
 def test_update_matches_the_reference_fixture(name, amd_lib, monkeypatch):
     """Three ``clf.update()`` calls on the device against the real reference (tests/golden/qgpo_cep.npz): each returned dict at rtol =
     atol = 1e-4, the first step's gradients at 2e-4 x max |g_ref| per parameter, the parameter and EMA checksums after the third call at

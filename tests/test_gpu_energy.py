@@ -32,7 +32,7 @@ def _spy_run(monkeypatch):
     return seen
 
 
-@pytest.mark.parametrize("name", ec.TABLE)
+@pytest.mark.parametrize("name", ec.GOLDEN_TABLE)
 def test_sample_matches_the_reference_fixture(name, amd_lib, monkeypatch):
     """x and log_p of ``agent.sample(...)`` on the device against what the real reference returned for the same inputs and draws
     (tests/golden/qgpo_guided.npz) at rtol = atol = 1e-4 -- served by ``try_energy_guided`` in one request."""

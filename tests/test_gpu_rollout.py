@@ -9,6 +9,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import rollout_cases as rc  # noqa: E402
+import tower_cases as tc  # noqa: E402
 from gpu_profile import profiled  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -155,3 +156,31 @@ def test_parameter_gradients_land_in_place_inside_a_scope(amd_lib, monkeypatch):
         err, scale = float((inside[n] - outside[n]).abs().max()), float(outside[n].abs().max())
         print(f"  {n}: max|d| {err:.3e}, max|g| {scale:.3e}")
         assert err <= 1e-6 * scale, (n, err, scale)
+
+
+def test_weights_off_16_byte_alignment_give_the_aligned_results(amd_lib, monkeypatch):
+    """``_trunk`` admits a contiguous weight wherever it starts.  With every Linear weight at element offset 1 of a flat buffer (K a
+    multiple of 4 in every layer: F = W = 512, so only the base address turns the float4 weight loads off) the fused route takes the
+    request, and actions, d / d obs and every parameter gradient equal the aligned run to 1e-6 relative."""
+    name = "limits_b17_a64_f512_w512_s2"
+    case = rc.CASES[name]
+    seen = _spy_forward(monkeypatch)
+    weight = torch.ones(case.B, device=DEV)
+    runs = []
+    for unaligned in (False, True):
+        agent, inp = rc.build(case, amd_lib, DEV)
+        if unaligned:
+            tc.repoint_off_alignment(agent.model["diffusion"])
+        obs = inp.obs.clone().requires_grad_(True)
+        act = rc.sample(agent, case, inp, obs)
+        rc.objective(act, inp, weight).backward()
+        torch.cuda.synchronize()
+        got = {n: p.grad.clone() for n, p in agent.model["diffusion"].named_parameters() if p.grad is not None}
+        got["obs"], got["act"] = obs.grad.clone(), act.detach().clone()
+        runs.append(got)
+    assert len(seen) == 2, "the fused route did not take both requests"
+    assert set(runs[0]) == set(runs[1]) and len(runs[0]) == 14
+    for n, want in runs[0].items():
+        err, scale = float((runs[1][n] - want).abs().max()), float(want.abs().max())
+        print(f"  {n}: max|d| {err:.3e}, max|aligned| {scale:.3e}")
+        assert scale > 0 and err <= 1e-6 * scale, (n, err, scale)

@@ -103,6 +103,29 @@ def test_reduction_matches_float64_on_the_kernels_own_scores(name, temperature):
         _check_reduction(E, q, f"{name} {mode} T={temperature}", cand.cpu().double())
 
 
+@pytest.mark.parametrize("path", ["given_scores", "fused"])
+def test_the_reduction_at_its_limits_k1024_top16(path):
+    """K = 1024 uses all 16 `taken` bits of every lane and ``top_k = 16`` all 16 ranks: argmax, sample and topk_mean at temperatures 1, 20
+    and 300 through ``cdx_select_f32`` over given scores (one launch) and behind the critic (64 tiles per state, two launches)."""
+    from cleandiffuser_amd.engine import select as E
+    case = sc.CASES["mlp_s2_k1024"]
+    assert case.K == E.MAX_K
+    critic, obs, cand, u = _on_device(case)
+    scores = None
+    if path == "given_scores":
+        q = sc.request(E, case, critic, obs, cand, "none", 1.0)
+        E.native_score_select(q)
+        scores = q.scores.clone()
+    for mode, top_k in (("argmax", 1), ("sample", 1), ("topk_mean", E.MAX_TOPK)):
+        for temperature in sc.TEMPERATURES:
+            q = sc.request(E, case, critic, obs, cand, mode, temperature, top_k, u if mode == "sample" else None, scores=scores)
+            assert E.run(q) == (1 if path == "given_scores" else 2)
+            torch.cuda.synchronize()
+            if mode == "topk_mean":
+                assert q.index.shape == (case.S, E.MAX_TOPK) and all(len(set(row)) == E.MAX_TOPK for row in q.index.tolist())
+            _check_reduction(E, q, f"k1024 {path} {mode} T={temperature}", cand.cpu().double())
+
+
 def test_given_scores_with_ties_and_a_strided_payload():
     """``cdx_select_f32`` alone over scores with exact ties: the first maximum, the top 4 with the lowest index on ties, the payload read
     through a row stride wider than P."""

@@ -68,12 +68,8 @@ def _buffers(q, scale):
     return out
 
 
-@pytest.mark.parametrize("name", tc.TABLE)
-def test_the_kernels_match_the_float64_restatements(name):
-    """``native_forward`` / ``native_backward`` against ``reference_forward`` / ``reference_backward`` in float64 on the CPU at rtol = atol =
-    1e-4: out, H_l, P_l, rstd_l, R G_l, R Sb_l, R Sg_l and R g_x of every tower."""
+def _assert_kernels_match_float64(name, case):
     from cleandiffuser_amd.engine import tower
-    case = tc.CASES[name]
     want = _run(tower, case, "cpu", torch.float64, native=False)
     got = _run(tower, case, DEV, torch.float32, native=True)
     torch.cuda.synchronize()
@@ -83,6 +79,77 @@ def test_the_kernels_match_the_float64_restatements(name):
         a, b = g[what].cpu().double().numpy(), w[what].numpy()
         print(f"  {name} {what}: max|d| {float(np.abs(a - b).max()):.3e}  max|ref| {float(np.abs(b).max()):.3e}")
         np.testing.assert_allclose(a, b, rtol=1e-4, atol=1e-4, err_msg=what)
+
+
+@pytest.mark.parametrize("name", tc.TABLE)
+def test_the_kernels_match_the_float64_restatements(name):
+    """``native_forward`` / ``native_backward`` against ``reference_forward`` / ``reference_backward`` in float64 on the CPU at rtol = atol =
+    1e-4: out, H_l, P_l, rstd_l, R G_l, R Sb_l, R Sg_l and R g_x of every tower."""
+    _assert_kernels_match_float64(name, tc.CASES[name])
+
+
+# below 48 KiB, 50.5 KiB, below 48 KiB again, 64.5 KiB (the largest plan two images [16][512 + 4] can make)
+HIGH_WATER = [("twinq_like_r16_k20", None), ("w400_r17_k20", tc._c(17, 20, [400, 1], ["mish", None])), ("v_like_r1_k32", None),
+              ("limits_r17_k512", None)]
+
+
+def _high_water_sequence():
+    """(run in a process of its own) the requests of HIGH_WATER in order, each against float64."""
+    from cleandiffuser_amd.engine import tower
+    for name, case in HIGH_WATER:
+        case = tc.CASES[name] if case is None else case
+        towers = tc.build(case)
+        print(name, "LDS bytes", tower.lds_bytes(tower.describe(towers[0])))
+        _assert_kernels_match_float64(name, case)
+
+
+def test_the_lds_attribute_follows_the_largest_request_of_the_process():
+    """``ro_launch_tiles`` raises the kernel's dynamic-LDS attribute only past its own high-water mark, which lives as long as the
+    process: a fresh process runs, on both tower kernels, a request below 48 KiB, one of 50.5 KiB, one below 48 KiB again and then one of
+    64.5 KiB -- each equal to its float64 reference at rtol = atol = 1e-4."""
+    import subprocess
+    from cleandiffuser_amd.engine import tower
+    sizes = [tower.lds_bytes(tower.describe(tc.build(tc.CASES[n] if c is None else c)[0])) for n, c in HIGH_WATER]
+    assert sizes[0] < 48 * 1024 < sizes[1] < sizes[3] and sizes[2] < 48 * 1024 and sizes[3] == 2 * 16 * 516 * 4, sizes
+    here = os.path.dirname(os.path.abspath(__file__))
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.dirname(here), here, os.environ.get("PYTHONPATH", "")]))
+    out = subprocess.run([sys.executable, "-c", "import test_gpu_tower as t; t._high_water_sequence()"], cwd=here, env=env, capture_output=True,
+                         text=True, timeout=300)
+    print(out.stdout[-4000:], out.stderr[-2000:])
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert [line.split()[0] for line in out.stdout.splitlines() if "LDS bytes" in line] == [n for n, _ in HIGH_WATER]
+
+
+@pytest.mark.parametrize("name", ["twinq_like_r16_k20", "limits_r17_k512"])
+def test_weights_off_16_byte_alignment_give_the_aligned_results(name, monkeypatch):
+    """K a multiple of 4 in every layer, so only the base address turns the float4 weight loads off: with every Linear weight at element
+    offset 1 of a flat buffer ``try_tower`` takes the request, and outputs, g_x and every parameter gradient equal the aligned run to
+    1e-6 relative."""
+    from cleandiffuser_amd.engine import tower
+    monkeypatch.setenv("CDX_TOWER", "1")
+    seen = _spy_forward(monkeypatch)
+    case = tc.CASES[name]
+    assert case.k0 % 4 == 0 and all(w % 4 == 0 for w in case.widths[:-1])
+    x0, g_out = tc.make_inputs(case)
+    runs = []
+    for unaligned in (False, True):
+        towers = tc.build(case, device=DEV)
+        for seq in towers if unaligned else []:
+            tc.repoint_off_alignment(seq)
+        x = x0.to(DEV).requires_grad_(True)
+        outs = tower.try_tower(towers, x)
+        assert outs is not None and len(seen) == 1 + unaligned, "the fused route did not take this request"
+        sum((o * g.to(DEV)).sum() for o, g in zip(outs, g_out)).backward()
+        torch.cuda.synchronize()
+        got = {f"out[{t}]": o.detach().clone() for t, o in enumerate(outs)}
+        got["g_x"] = x.grad.clone()
+        got.update({f"{t}.{n}": p.grad.clone() for t, seq in enumerate(towers) for n, p in seq.named_parameters()})
+        runs.append(got)
+    assert set(runs[0]) == set(runs[1])
+    for n, want in runs[0].items():
+        err, scale = float((runs[1][n] - want).abs().max()), float(want.abs().max())
+        print(f"  {name} {n}: max|d| {err:.3e}, max|aligned| {scale:.3e}")
+        assert scale > 0 and err <= 1e-6 * scale, (n, err, scale)
 
 
 @pytest.mark.parametrize("name", ["dql_like_r17_k7", "unequal_r33", "depth6_r17"])

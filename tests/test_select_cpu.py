@@ -195,12 +195,7 @@ def _c_side():
     return E, E._lib()
 
 
-def _c_request(E, O=7, A=3, widths=(16, 1), S=4, K=5, **sel):
-    g = E.CdxScoreSelect(O=O, A=A, n_towers=1, n_layers=len(widths))
-    g.sel = E.CdxSelect(S=S, K=K, temperature=1.0, **sel)
-    for l, w in enumerate(widths[:E.tower.MAX_LAYERS]):
-        g.width[l], g.eps[l] = w, 1e-5
-    return g
+_c_request = sc.c_request
 
 
 def test_select_validation_fails_loudly():

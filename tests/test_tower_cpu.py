@@ -283,11 +283,7 @@ def _c_side():
     return tower, tower._lib()
 
 
-def _c_request(tower, k0, widths, norms=None, acts=None, **kw):
-    g = tower.CdxTower(R=4, K0=k0, n_towers=1, n_layers=len(widths), **kw)
-    for l, w in enumerate(widths):
-        g.width[l], g.norm[l], g.act[l], g.eps[l] = w, int(norms[l]) if norms else 0, acts[l] if acts else 0, 1e-5
-    return g
+_c_request = tc.c_request
 
 
 def test_lds_plan_matches_the_c_side():

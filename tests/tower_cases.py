@@ -1,6 +1,7 @@
-"""The towers the critic-tower tests share (engine/tower.py, csrc/cdx_tower.hip): small on purpose -- the 512-wide case has the most
-rows, 33.  Every case builds its ``nn.Sequential`` towers from a seed, scales the input so that tanh and the norm are not in a trivial
-regime, and says which side takes a gradient."""
+"""The towers the critic-tower tests share (engine/tower.py, csrc/cdx_tower.hip): small on purpose -- no case has more
+than 33 rows, the ENVELOPE group at the edges of the admitted sizes (K0 and widths up to 512, a last width up to 64) included.  Every
+case builds its ``nn.Sequential`` towers from a seed, scales the input so that tanh and the norm are not in a trivial regime, and says
+which side takes a gradient."""
 from types import SimpleNamespace
 
 import torch
@@ -31,6 +32,22 @@ CASES = {
     "frozen_x_grad": _c(17, 7, [32, 32, 32, 1], ["tanh", "mish", "mish", None], towers=2, frozen=True, x_grad=True),
     "trainable_no_x_grad": _c(33, 20, [48, 48, 1], ["mish", "mish", None], towers=2, x_grad=False),
 }
+# the edges of what tower_plan / tw_check_layers admit (K0 <= 512, widths <= 512, last width <= 64, LDS <= 160 KiB)
+ENVELOPE = {
+    # every limit at once: 64.5 KiB of LDS, both sweeps of the product in every layer, a 4-tile last layer, 32 K blocks
+    "limits_r17_k512": _c(17, 512, [512, 512, 64], ["mish", "tanh", None], towers=2),
+    # the kitchen DQLCritic (obs 60 + act 9): five K blocks with a ragged end through the scalar weight loads
+    "kitchen_r33_k69": _c(33, 69, [256, 256, 256, 1], ["tanh", "mish", "mish", None], towers=2),
+    # a last layer of 33 columns (three column tiles, zero up to 48 for the transposed product) behind a normed first layer
+    "wide_last_r17_k33": _c(17, 33, [48, 33], ["mish", None], norm=[True, False]),
+    # the same with the norm and an activation on the wide last layer itself
+    "wide_last_norm_r17_k33": _c(17, 33, [48, 33], ["mish", "tanh"], norm=[True, True]),
+    # the smallest input
+    "k1_r16": _c(16, 1, [16, 1], ["mish", None]),
+    # a partial second sweep (272 = 17 column tiles) over K0 = 85 (F of the kitchen DQLMlp: six K blocks, ragged)
+    "sweep272_r17_k85": _c(17, 85, [272, 272, 17], ["silu", "mish", None]),
+}
+CASES.update(ENVELOPE)
 TABLE = list(CASES)
 
 
@@ -96,3 +113,23 @@ def check_regime(tower, case):
         else:
             big = big or float(q.P[0][l].abs().max()) > 1.0
     assert big
+
+
+def c_request(tower, k0, widths, norms=None, acts=None, **kw):
+    """A ``CdxTower`` of sizes alone (every pointer null): what the C side's size checks and LDS plan read."""
+    g = tower.CdxTower(R=4, K0=k0, n_towers=1, n_layers=len(widths), **kw)
+    for l, w in enumerate(widths):
+        g.width[l], g.norm[l], g.act[l], g.eps[l] = w, int(norms[l]) if norms else 0, acts[l] if acts else 0, 1e-5
+    return g
+
+
+def repoint_off_alignment(module):
+    """Every nn.Linear weight of `module` becomes a view at element offset 1 of a flat fp32 buffer of its own: contiguous, same values,
+    and a base address that is 4 bytes past a 16-byte boundary."""
+    for m in module.modules():
+        if isinstance(m, nn.Linear):
+            flat = torch.empty(m.weight.numel() + 1, device=m.weight.device, dtype=m.weight.dtype)
+            view = flat[1:].view(m.weight.shape)
+            view.copy_(m.weight.detach())
+            m.weight.data = view
+            assert m.weight.is_contiguous() and m.weight.data_ptr() % 16 == 4
