@@ -1,4 +1,4 @@
-// cdx_rowtile.h -- what the row-tile kernels share (cdx_rollout.hip, cdx_energy.hip, cdx_cep.hip, cdx_tower.hip, cdx_select.hip, cdx_critic_step.hip; cdx_energy_mlp.h and cdx_tower_layers.h build on it): one
+// cdx_rowtile.h -- what the row-tile kernels share (cdx_rollout.hip, cdx_energy.hip, cdx_cep.hip, cdx_tower.hip, cdx_select.hip, cdx_critic_step.hip, cdx_regress_step.hip; cdx_energy_mlp.h and cdx_tower_layers.h build on it): one
 // workgroup of 4 wave64 owns 16 rows, activations live in LDS, weights are read from global memory (L2-resident, the same for every
 // workgroup), products run on v_mfma_f32_16x16x4_f32 (exact fp32, rows on the M axis; lane maps: cdx_probe_mfma_layout).  Device side: the
 // product routine, the tile strides and loader, and what the sampling kernels need to run the solver step of cdx_step.h on their (16 x A) state

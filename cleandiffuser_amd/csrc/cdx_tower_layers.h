@@ -2,7 +2,8 @@
 // for the kernels that run them: cdx_tower_fwd_kernel / cdx_tower_bwd_kernel (cdx_tower.hip: a training forward, which saves what the
 // backward reads, and that backward), cdx_score_select_kernel (cdx_select.hip: the critic in front of the candidate selection, which keeps
 // the last layer's image only) and cdx_critic_step_kernel (cdx_critic_step.hip: target, forward, loss and backward-data of a critic step in
-// one launch, P_l and rstd_l staying in LDS).  Forward, per layer: z = h W^T + b (ro_product<false>); with a norm, 16 lanes per row take the
+// one launch, P_l and rstd_l staying in LDS) and cdx_regress_step_kernel (cdx_regress_step.hip: the same for an MSE step against a given
+// target, a last width up to 64).  Forward, per layer: z = h W^T + b (ro_product<false>); with a norm, 16 lanes per row take the
 // mean and then the biased variance of the centred values over the row in LDS (two passes, a fixed butterfly), xhat = (z - mean) rstd,
 // y = xhat gamma + beta; h = act(y).  Backward, per layer from the top: y from the saved P_l (xhat or z), dy = dH act'(y), with a norm
 // g = dy gamma, dz = rstd (g - mean(g) - xhat mean(g xhat)) and the tile's column sums of dy and dy xhat (rows in order), then

@@ -5,7 +5,10 @@ per-class default learning rate is computed but unused (invdynamic/mlp.py:47-52)
 
 ``predict`` on a ROCm device runs the chain through engine/heads.py (fp32-MFMA GEMMs with fused bias + activation, fused
 LayerNorm); ``update`` keeps the reference's autograd graph with every Linear / LayerNorm / activation node on the library's kernels
-(engine/train.py:chain_forward) and steps through ``FusedAdam`` (``cdx_optim_f32``).
+(engine/train.py:chain_forward) and steps through ``FusedAdam`` (``cdx_optim_f32``).  ``MlpInvDynamic.update`` and
+``EnsembleMlpInvDynamic.update_idx`` first offer the step to the fused launch of engine/regress_step.py (load, forward, MSE, backward-data
+in one kernel; utils/regression_steps.py says where it is on by default, ``CDX_REGRESS_STEP=0`` switches it off); the GELU heads are
+refused there and run the body above unchanged.
 """
 import torch
 import torch.nn as nn
@@ -44,6 +47,13 @@ class _MseTrainedHead:
     """update/predict/train/eval/save/load shared by the heads; subclasses provide ``forward`` and ``_net``."""
 
     def update(self, o, a, o_next):
+        # (one launch for load, forward, loss and backward-data where utils/regression_steps.py switches it on and the net is taken:
+        #  MlpInvDynamic; the GELU heads are refused and run the lines below)
+        from ..utils.regression_steps import fused_step
+        out = fused_step(self._net(), self.optim, o, o_next, a, "invdyn")
+        if out is not None:
+            self.optim.step()
+            return {"loss": out["loss"].item()}
         self.optim.zero_grad()
         loss = ((self.forward(o, o_next) - a) ** 2).mean()
         loss.backward()
@@ -146,6 +156,11 @@ class EnsembleMlpInvDynamic(MlpInvDynamic):
         return sum(_forward_rows(m, x) for m in self.mlp) / self.n_models
 
     def update_idx(self, idx, o, a, o_next):
+        from ..utils.regression_steps import fused_step
+        out = fused_step(self.mlp[idx], self.optim, o, o_next, a, "invdyn_ensemble")      # (as _MseTrainedHead.update)
+        if out is not None:
+            self.optim.step()
+            return out["loss"].item()
         self.optim.zero_grad()
         loss = ((self.forward(o, o_next, idx) - a) ** 2).mean()
         loss.backward()

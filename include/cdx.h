@@ -1108,6 +1108,50 @@ long long cdx_critic_step_lds_bytes(const cdx_critic_step* g);
 int cdx_critic_step_f32(const cdx_critic_step* g, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * A supervised MSE training step of one tower against a GIVEN target in ONE launch (csrc/cdx_regress_step.hip).  Purely additive
+ * entries: no existing struct or call changes, so CDX_ABI_VERSION stays 19.  Reference: ``invdyn.update(obs, act, next_obs)`` of
+ * pipelines/dd_d4rl_*.py:89-90 and veteran_d4rl_*.py:253/263/474 (invdynamic/mlp.py:54-60: MlpInvDynamic) and the critic's inner loop of
+ * pipelines/sfbc_d4rl_mujoco.py:144-149: rows [x0 | x1] through a Linear -> [LayerNorm] -> activation tower, mean((out - y)^2), backward.
+ * One workgroup of 4 wave64 owns 16 rows: grid ceil(R / 16).  Four phases:
+ *   load      [x0 | x1] of the tile's rows (net.K0 == x0.width + x1.width; x1.width == 0: x0 alone) and x_cat (R, net.K0).  x0, x1 and y
+ *             are cdx_regress_rows: batch row r starts at float ((r / inner) period + r % inner) ld of `ptr` -- a (R, width) matrix of
+ *             row stride s is (inner 1, period 1, ld s) (obs[:, 0] of a (B, H, D) batch: ld H D, the same rows as inner 1, period H,
+ *             ld D); obs[:, :-1] / obs[:, 1:] of that batch are (inner H - 1, period H, ld D), the second with its pointer D floats on;
+ *   forward   the tower (net.n_towers == 1), as cdx_tower_fwd_f32: H_l (layer-major as cdx_tower's, layers 0 .. n_layers - 2) and
+ *             out (R, W), W = the last width.  P_l and rstd_l stay in LDS;
+ *   loss      e = out - y, d_out = 2 e / (R W); loss_part[tile] = (the sum of e^2 over the tile, row-major) / (R W): the sum over the
+ *             tiles is the step's loss;
+ *   backward  from d_out, as cdx_tower_bwd_f32 with want_params and without g_x: G_l, Sb, Sg in cdx_tower's layout.
+ * The weight / bias gradients are the caller's: one cdx_conv_wgrad_batch_f32 with jobs (G_l, H_{l-1} or x_cat, R); the gain / shift
+ * gradients and the loss one cdx_colsum_batch_f32 over Sg / Sb / loss_part.  Caller-owned memory, one kernel per call enqueued on
+ * `hip_stream`, no synchronisation, no allocation; no atomics, one fixed lane and order per element: bit-reproducible.
+ * Limits (CDX_EINVAL with a message, before anything is launched): the net within the limits of cdx_tower (last width 1 .. 64) with
+ * one tower and 1 <= K0 <= 512; x0.width >= 1; y.width == the last width; inner >= 1, period >= inner and ld >= 1 for every operand
+ * that has columns; R <= 2^31 - 17; the LDS plan (cdx_regress_step_lds_bytes: two activation images, P_l and rstd_l, the 16 x 64 out
+ * tile) at most 160 KiB.  R == 0 is CDX_OK.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct cdx_regress_rows {
+    const float* ptr;
+    int32_t width, ld;                                  /* columns read; floats between two rows */
+    int32_t inner, period;                              /* batch row r is row (r / inner) period + r % inner */
+} cdx_regress_rows;
+typedef struct cdx_regress_step {
+    int32_t R, reserved;
+    cdx_critic_net net;                                 /* n_towers == 1 */
+    cdx_regress_rows x0, x1, y;                         /* x1.width == 0 with x1.ptr == NULL: the rows are x0 alone */
+    float* out;                                         /* (R, W) */
+    float* loss_part;                                   /* (ceil(R / 16)) */
+    float* x_cat;                                       /* (R, net.K0) */
+    float* H;                                           /* as cdx_tower */
+    float* G;
+    float* Sb;
+    float* Sg;
+} cdx_regress_step;
+/* bytes of LDS one workgroup of this request needs, or a negative CDX_E* code when the sizes are out of range */
+long long cdx_regress_step_lds_bytes(const cdx_regress_step* g);
+int cdx_regress_step_f32(const cdx_regress_step* g, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
  * The denoising loss of the row-MLP denoisers in one forward and one backward launch (csrc/cdx_denoise.hip).  Purely additive entries:
  * no existing struct or call changes, so CDX_ABI_VERSION stays 19.  Reference: ``bc_loss = actor.loss(act, obs)`` of
  * pipelines/dql_d4rl_*.py and edp_d4rl_mujoco.py:97 (diffusion/diffusionsde.py:94-110 over nn_diffusion/dqlmlp.py:30-52 /
